@@ -19,7 +19,16 @@ Workloads (config.workload):
            every rank merges the key range it owns.
 
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload ...]
+                       [--full] [--dump-outputs DIR]
        (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full
+adds the figures that take work of their own: the CPU baseline (oracle and, where it was
+built, the reference's engine), the per-table materialisation of config3l / config4s,
+the drain of every group of config4 / 4s after the last step and the second operator
+of config5 / 5w.  --dump-outputs DIR writes the result rows of the last timed step as
+DIR/<column>.npy (float64, rows sorted by key; a fixed, seeded sample of at most
+OUTPUT_SAMPLE_ROWS rows when there are more).
 """
 import argparse
 import json
@@ -51,6 +60,18 @@ QUERIES = {
 }
 
 
+# names of the result columns (--dump-outputs), in the order of the SELECT list
+OUTPUT_COLUMNS = {
+    "config2": ["k", "sum_v", "count"],
+    "config3": ["k", "sum_v", "count", "sum_b"],
+    "config3l": ["k", "sum_v", "count", "sum_b"],
+    "config4": ["u", "sum_a", "count", "sum_v"],
+    "config4s": ["s", "sum_a", "count", "sum_v"],
+    "config5": ["items_position", "count", "sum_items_price"],
+    "config5w": ["n", "count", "sum_s"],
+}
+
+
 def config5_plan():
     from eventql_amd import capi as K
     from eventql_amd.plan import Plan, col, count, sum_
@@ -68,6 +89,51 @@ def config5w_plan():
     return Plan(S, scan_select=[count(col("items.position")), sum_(col("items.price"))],
                 select=[out(0), count(1), sum_(out(1))], group_by=[out(0)],
                 scan_mode=K.SCAN_NESTED_WITHIN_RECORD, groups_hint=16)
+
+
+# --dump-outputs: 1.5e6 rows x 4 float64 columns = 48 MB at most
+OUTPUT_SAMPLE_ROWS = 1_500_000
+OUTPUT_SAMPLE_SEED = 20240607
+
+
+def svector_to_f64(stype, data):
+    """packed SVector bytes of one result column -> float64 array, NaN for NULL; a
+    string becomes a 53-bit hash of its bytes (exact in float64)"""
+    import hashlib
+    import numpy as np
+    from eventql_amd import capi as K
+    from eventql_amd.plan import unpack_svector
+    codes = {K.T_UINT64: "<u8", K.T_TIMESTAMP64: "<u8", K.T_INT64: "<i8", K.T_FLOAT64: "<f8",
+             K.T_BOOL: "u1"}
+    if stype in codes:
+        rec = np.frombuffer(data, dtype=np.dtype([("v", codes[stype]), ("t", "u1")]))
+        out = rec["v"].astype(np.float64)
+        out[(rec["t"] & K.STAG_NULL) != 0] = np.nan
+        return out
+    vals = unpack_svector(stype, data)
+    if stype == K.T_STRING:
+        vals = [None if s is None else
+                float(int.from_bytes(hashlib.blake2b(s, digest_size=8).digest(), "little") >> 11)
+                for s in vals]
+    return np.array([np.nan if v is None else float(v) for v in vals], dtype=np.float64)
+
+
+def dump_outputs(dirname, names, types, raws):
+    """result rows (packed SVector bytes per column, as nextBatch delivers them) ->
+    dirname/<name>.npy, float64 (NaN = NULL), rows sorted by the key column (the first),
+    at most OUTPUT_SAMPLE_ROWS of them (a seeded sample, the same for the same rows),
+    and dirname/num_rows.npy, the number of result rows"""
+    import numpy as np
+    cols = [svector_to_f64(t, raw) for t, raw in zip(types, raws)]
+    n = len(cols[0]) if cols else 0
+    order = np.lexsort(cols[::-1]) if n else np.zeros(0, dtype=np.int64)
+    if n > OUTPUT_SAMPLE_ROWS:
+        rng = np.random.default_rng(OUTPUT_SAMPLE_SEED)
+        order = order[np.sort(rng.choice(n, size=OUTPUT_SAMPLE_ROWS, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for name, c in zip(names, cols):
+        np.save(os.path.join(dirname, name + ".npy"), c[order])
+    np.save(os.path.join(dirname, "num_rows.npy"), np.array([n], dtype=np.float64))
 
 
 REFERENCE_SQL = {
@@ -137,8 +203,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=0, help="rows per GPU (0 = workload default)")
     ap.add_argument("--workload", default="config3", choices=sorted(QUERIES))
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take work of their own: CPU baseline, "
+                         "materialisation, drain of every group, second operator")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result rows of the last timed step as DIR/<column>.npy")
     ap.add_argument("--cpu-sample-rows", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --rows per GPU; strong: --rows in total, split over the GPUs")
     ap.add_argument("--no-hint", action="store_true",
@@ -225,20 +297,10 @@ def main():
         table = ctx.open_image(w.image())
         w.close()
         del c
-        ctx.synchronize()
-        t0m = time.perf_counter()
-        table.query(plan_fn()).close()
-        ctx.synchronize()
-        materialize_ms = (time.perf_counter() - t0m) * 1e3
     elif string_keys:
         # generated in HBM and encoded by the device writer; the first operator finds
         # the value boundaries of the STRING_PLAIN stream and hashes the keys, once
         table = B.string_key_table(ctx, rows, n_keys, seed)
-        ctx.synchronize()
-        t0m = time.perf_counter()
-        table.query(plan_fn()).close()
-        ctx.synchronize()
-        materialize_ms = (time.perf_counter() - t0m) * 1e3
     elif nested:
         # `rows` = records; written by the host writer (levels + LEB128 / bit-packed
         # data), then resident in HBM like any other table
@@ -246,6 +308,14 @@ def main():
         table = ctx.open_image(nested_image)
     else:
         table = ctx.generate(rows, columns, seed=seed, **gen_kw)
+    if args.full and (leb or string_keys):
+        # the once-per-table work of the first operator (re-encoding / key hashing),
+        # timed by itself; a plain run leaves it to the operator below
+        ctx.synchronize()
+        t0m = time.perf_counter()
+        table.query(plan_fn()).close()
+        ctx.synchronize()
+        materialize_ms = (time.perf_counter() - t0m) * 1e3
     ctx.synchronize()
     t0q = time.perf_counter()
     q = table.query(plan_fn())
@@ -256,17 +326,20 @@ def main():
     xchg = D.make_exchange(ctx) if world > 1 else None
     xmode = K.EXCHANGE_BY_OWNER if high_card else K.EXCHANGE_GATHER_ALL
 
-    def drain(qq):
+    def drain(qq, keep=None):
         n = 0
         while True:
-            k, _ = qq.next_batch(1024)
+            k, raw = qq.next_batch(1024)
             if k == 0:
                 return n
             n += k
+            if keep is not None:
+                keep.append(raw)
 
     per_query = args.workload == "config5w"
 
-    def step():
+    def step(keep=None):
+        # keep: a list that receives the packed result batches the step delivers
         if per_query and world == 1:
             # the per-record reduction belongs to the operator, not to the table: a
             # step builds the operator (kernel from the cache), reduces the records,
@@ -274,7 +347,7 @@ def main():
             qq = table.query(plan_fn())
             qq.launch()
             qq.finish()
-            n = drain(qq)
+            n = drain(qq, keep)
             step.stats = qq.stats()
             # both kernels of the operator: k_within_record (per-record reduction) and
             # evql_scan_agg (the GROUP BY over the per-record values)
@@ -286,12 +359,12 @@ def main():
         if world == 1:
             # 1e7 result rows are not pulled through nextBatch inside the timed
             # region (the reference puts ORDER BY / LIMIT above such a GROUP BY)
-            return q.stats()["num_groups"] if high_card else drain(q)
+            return q.stats()["num_groups"] if high_card else drain(q, keep)
         # partial aggregates -> records bucketed by owner (high cardinality) or sent to
         # everybody (low) -> merged in rank order; low: rank 0's result is the answer,
         # high: the result stays distributed over the ranks
         q.exchange(xchg, xmode)
-        return q.stats()["num_groups"] if high_card else drain(q)
+        return q.stats()["num_groups"] if high_card else drain(q, keep)
 
     for _ in range(args.warmup):
         step()
@@ -299,9 +372,11 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    # --dump-outputs: the result batches of the last timed step
+    last = [] if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        ngroups_out = step()
+    for i in range(args.steps):
+        ngroups_out = step(last if i == args.steps - 1 else None)
         kernel_ms.append(getattr(step, "kernel_ms", None) or q.stats()["kernel_ms"])
     torch.cuda.synchronize()
     if world > 1:
@@ -319,16 +394,24 @@ def main():
 
     stats = getattr(step, "stats", None) or q.stats()
     drain_info = None
-    if high_card and world == 1:
+    if high_card and world == 1 and (args.full or last is not None):
         # OUTSIDE ms_per_step: every group of the last step pulled through nextBatch
         # (GroupByExpression::nextBatch -> packed SVector bytes, 1024 rows per call as the
         # reference's ResultCursor asks)
         torch.cuda.synchronize()
         t0d = time.perf_counter()
-        nd = drain(q)
+        nd = drain(q, last)
         ddt = time.perf_counter() - t0d
         drain_info = dict(groups=int(nd), drain_ms=ddt * 1e3, groups_per_s=nd / ddt,
                           batch_rows=1024)
+    elif high_card and rank == 0 and last is not None:
+        # the groups rank 0 owns after the exchange
+        drain(q, last)
+    if rank == 0 and last is not None:
+        nc = q.column_count()
+        dump_outputs(args.dump_outputs, OUTPUT_COLUMNS[args.workload],
+                     [q.column_type(i) for i in range(nc)],
+                     [b"".join(b[i] for b in last) for i in range(nc)])
     if rank == 0:
         total_rows = rows * world * args.steps
         avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
@@ -405,7 +488,7 @@ def main():
                 "kernel_ms": avg_kernel_ms,
             },
         }
-        if world == 1 and not args.no_cpu_baseline and not leb:
+        if world == 1 and args.full and not args.no_cpu_baseline and not leb:
             if string_keys:
                 import oracle_lib as O
                 n_s = args.cpu_sample_rows or 4_000_000
@@ -446,7 +529,7 @@ def main():
             # the scan kernels' device time
             out_x["scan_kernel_ms"] = avg_kernel_ms
             out["config"]["exchange_last_step"] = out_x
-        if leb or string_keys:
+        if materialize_ms is not None:
             out["config"]["materialize_ms_first_operator"] = materialize_ms
         if string_keys:
             out["config"]["encodings"] = ("s STRING_PLAIN (value boundaries, 64-bit hashes and the exact "
@@ -457,13 +540,14 @@ def main():
             # the first operator over these columns is created (together with the
             # hiprtc compile of the plan) and is cached on the table; later operators
             # reuse the flattened columns
-            ctx.synchronize()
-            t0p = time.perf_counter()
-            q2 = table.query(plan_fn())
-            ctx.synchronize()
             out["config"]["first_operator_ms_flatten_and_jit"] = first_operator_ms
-            out["config"]["next_operator_ms"] = (time.perf_counter() - t0p) * 1e3
-            q2.close()
+            if args.full:
+                ctx.synchronize()
+                t0p = time.perf_counter()
+                q2 = table.query(plan_fn())
+                ctx.synchronize()
+                out["config"]["next_operator_ms"] = (time.perf_counter() - t0p) * 1e3
+                q2.close()
             out["config"]["records_per_gpu"] = rows
             out["config"]["flattened_rows_per_gpu"] = int(stats["rows_scanned"])
             out["config"]["encodings"] = "levels bit-packed, position UINT32_BITPACKED(4b), price LEB128"

@@ -11,7 +11,7 @@ cd "$ROOT"
 b() {  # b <name> <bench args...>
   local name=$1; shift
   echo "[measure] $name"; date
-  python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { tail -5 "$OUT/bench_$name.err"; return 1; }
+  python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { tail -5 "$OUT/bench_$name.err"; return 1; }
 }
 if [ "$PART" = 1 ]; then
   b config3 --steps 20 --warmup 3
@@ -32,13 +32,13 @@ else
     local name=$1; shift
     echo "[measure] kernel trace $name"; date
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$name" -- \
-      python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$OUT/kt_$name.log" 2>&1
+      python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$OUT/kt_$name.log" 2>&1
   }
   pmc() {  # pmc <counter> <name> <bench args...>
     local ctr=$1 name=$2; shift 2
     echo "[measure] pmc $ctr $name"; date
     rocprofv3 --pmc "$ctr" --output-format csv -d "$OUT/pmc_${ctr}_$name" -- \
-      python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$OUT/pmc_${ctr}_$name.log" 2>&1
+      python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$OUT/pmc_${ctr}_$name.log" 2>&1
   }
   kt config3 --steps 10 --warmup 2
   kt config4 --steps 5 --warmup 1 --workload config4

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
   --output-format csv -d "$OUT/sq_$WL" -- \
-  python3 "$ROOT/bench.py" --workload "$WL" --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/sq_$WL.log" 2>&1
+  python3 "$ROOT/bench.py" --full --workload "$WL" --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/sq_$WL.log" 2>&1
 python3 - "$OUT/sq_$WL" <<'PY'
 import csv, glob, os, sys, collections
 d = sys.argv[1]
