@@ -536,7 +536,8 @@ static int create_one(evql_ctx_t* ctx, evql_table_t* table, const evql_plan_desc
   q->groups_hint = plan->groups_hint;
   q->float_sum_mode = plan->float_sum_mode;
   q->float_sum_bound = plan->float_sum_bound;
-  if (plan->float_sum_mode > EVQL_FLOAT_SUM_EXACT || !(plan->float_sum_bound >= 0)) {
+  if (plan->float_sum_mode > EVQL_FLOAT_SUM_EXACT || !(plan->float_sum_bound >= 0) ||
+      !std::isfinite(plan->float_sum_bound)) {
     return fail(EVQL_EARG, "bad float sum mode / bound");
   }
   q->row_begin = plan->row_begin;

@@ -1398,10 +1398,13 @@ static Status choose_exact_sum_scales(evql_query* q) {
       }
     }
     // quantum 2^e with bound * 2^-e < 2^61: |q| < 2^61, the high parts (|q| >> 31
-    // < 2^30) and the low parts (< 2^31) of up to 2^32 rows add up inside 64 bits
+    // < 2^30) and the low parts (< 2^31) of up to 2^32 rows add up inside 64 bits.
+    // e >= -1023 keeps the kernel's scale 2^-e finite (a bound below 2^-962 would make
+    // it +inf); terms of magnitude <= 2^-1024 then round to 0, and a subnormal total is
+    // -1, 0 or 1 quantum, which exact_sum_value scales without a second rounding
     int ex = 0;
     std::frexp(bound > 0 ? bound : 1.0, &ex);  // bound < 2^ex
-    q->fsum_exp[a.exact_index] = ex - 61;
+    q->fsum_exp[a.exact_index] = std::max(ex - 61, -1023);
     q->fsum_bound[a.exact_index] = bound;
   }
   return Status();

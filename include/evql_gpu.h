@@ -452,10 +452,14 @@ typedef struct {
    *                        depend on the order of the rows, the run, the number of
    *                        workgroups or -- with the same bound on every partition --
    *                        on how the table is split over GPUs.  Error <= rows * q / 2.
+   *                        q = 2^e, e = max(ex - 61, -1023) where 2^(ex-1) <= bound
+   *                        < 2^ex: the kernel's scale 2^-e stays finite for bounds
+   *                        below 2^-962, and terms of magnitude <= 2^-1024 round to 0.
    * float_sum_bound: an upper bound of |argument| over all rows; 0 = derived from the
    * table (maximum |value| of the columns the argument reads, through the
-   * expression); EVQL_ENOTSUP when no finite bound can be derived.  A row beyond the
-   * bound (or NaN / infinity) fails the query with EVQL_ERUNTIME. */
+   * expression); EVQL_ENOTSUP when no finite bound can be derived; a negative or
+   * non-finite bound is EVQL_EARG.  A row beyond the bound (or NaN / infinity) fails
+   * the query with EVQL_ERUNTIME. */
   uint32_t float_sum_mode;
   double float_sum_bound;
 } evql_plan_desc_t;

@@ -22,7 +22,11 @@
  *     skip NIL); over zero non-NULL inputs the result is NULL (value 0, tag 1);
  *     mean accumulates (double) value in row order and divides on get;
  *     float min/max also skip NaN inputs (the legacy `first value initialises`
- *     rule would make the result depend on where in the scan a NaN appears)
+ *     rule would make the result depend on where in the scan a NaN appears);
+ *     a zero min/max keeps the first zero met here, its sign is unspecified for
+ *     the HIP path (any zero of the group)
+ *   - a float sum starts at +0.0, so a group of zeros sums to +0.0; NaN or both
+ *     infinities give NaN (tests/float_edges.py holds the exact reference)
  * Deliberate non-reproductions of reference *bugs*:
  *   - the evaluateVector X_INPUT shortcut (vm.cc:189-199) is applied only to
  *     programs that are exactly a bare column reference, where it is
