@@ -324,6 +324,15 @@ bool buildPlanDesc(csql::Transaction* txn, csql::GroupByNode* group,
   d.group_mode = partial ? EVQL_MODE_PARTIAL : EVQL_MODE_FINAL;
 
   /* which reference scan operator is being replaced */
+  if (kind == ScanKind::PARTITION) {
+    /* a NO_AGGREGATION statement over a partition runs FastCSTableScan, whose rows over
+     * repeated columns are not restated: it stays a flat scan (and is declined by the
+     * library when it names a repeated column).  Every other statement runs CSTableScan
+     * under the cursor's row filter: a record scan over the chain. */
+    kind = seqscan->aggregationStrategy() == csql::AggregationStrategy::NO_AGGREGATION
+               ? ScanKind::FAST
+               : ScanKind::DREMEL;
+  }
   if (kind == ScanKind::FAST) {
     d.scan_mode = EVQL_SCAN_FLAT;
   } else {

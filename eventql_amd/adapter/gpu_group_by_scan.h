@@ -43,8 +43,10 @@ namespace evql_adapter {
 
 /* which reference scan operator the table's provider would have built */
 enum class ScanKind {
-  FAST,   /* FastCSTableScan (CSTableScanProvider.cc:38-54, partition_cursor.cc:199) */
-  DREMEL  /* CSTableScan     (partition_cursor.cc:206-213)                          */
+  FAST,      /* FastCSTableScan (CSTableScanProvider.cc:38-54, partition_cursor.cc:199) */
+  DREMEL,    /* CSTableScan     (partition_cursor.cc:206-213)                          */
+  PARTITION  /* PartitionCursor decides per statement (partition_cursor.cc:42-50):
+              * NO_AGGREGATION -> FastCSTableScan, anything else -> CSTableScan      */
 };
 
 /* one LSM file of a partition (db/partition_state.proto LSMTableRef) */

@@ -66,8 +66,9 @@ inline GpuTableRegistry::Resolver partitionResolver(SnapshotLookup find_snapshot
     RefPtr<eventql::PartitionSnapshot> snap = find_snapshot(table_name);
     if (!snap.get()) return false;
     /* PartitionCursor builds FastCSTableScan for NO_AGGREGATION statements and CSTableScan
-     * otherwise (:42-50, 197-213); evql_query_create_chain lowers the former */
-    *kind = ScanKind::FAST;
+     * otherwise (:42-50, 197-213): the statement decides, when its plan is lowered
+     * (buildPlanDesc); evql_query_create_chain takes both */
+    *kind = ScanKind::PARTITION;
     return chainFromSnapshot(*snap.get(), files, version_tag);
   };
 }

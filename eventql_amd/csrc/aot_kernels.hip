@@ -1448,6 +1448,57 @@ __global__ void __launch_bounds__(kBlock) k_lsm_filter(LsmArgs a) {
   }
 }
 
+// ---- row filters on nested scans (CSTableScan::setFilter, CSTableScan.cc:203-204, 426) ------
+// The reference reads filter_[record] once per record, and every flattened row of a
+// rejected record fails: a record mask.  The fused kernels test one bit per ROW, so the
+// record bits are expanded once per query to one bit per leaf slot.  One workgroup per
+// 2048-slot tile; the wave's lane l takes slot 64 * chunk + l of chunk (j, wave), so that a
+// ballot IS one word of the mask.  A slot's record = records started in front of the tile
+// (rec_offsets, the scan k_within_record uses) + level-0 slots of the tile up to and
+// including it - 1.  Every word of every tile is stored by lane 0 of its wave (plain vector
+// stores); slots behind nflat and records behind rec_len read as 0.  All threads reach the
+// barrier: bounds are conditions on loads, not exits.
+__global__ void __launch_bounds__(kBlock) k_filter_expand(const u8* levels, const u64* rec_offsets,
+                                                          u64 nflat, const u8* rec_bits,
+                                                          u64 rec_len, u64* row_bits) {
+  constexpr u32 kWaves = kBlock / 64, kChunks = kDecodeTile / kBlock;
+  __shared__ u32 s_cnt[kChunks * kWaves];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 tile = blockIdx.x;
+  const u64 base = tile * kDecodeTile;
+  u64 starts[kChunks];
+#pragma unroll
+  for (u32 j = 0; j < kChunks; ++j) {
+    const u64 s = base + (u64) j * kBlock + tid;
+    starts[j] = __ballot(s < nflat && levels[s] == 0);
+    if (lane == 0) s_cnt[j * kWaves + wave] = (u32) __popcll(starts[j]);
+  }
+  __syncthreads();
+  const u64 rec0 = rec_offsets[tile];
+  const u64 upto = (2ull << lane) - 1;  // lanes <= this one
+  u32 before = 0;                       // level-0 slots of the tile in the chunks of rows < j
+#pragma unroll
+  for (u32 j = 0; j < kChunks; ++j) {
+    u32 in_row = 0, row_total = 0;
+#pragma unroll
+    for (u32 w = 0; w < kWaves; ++w) {
+      const u32 c = s_cnt[j * kWaves + w];
+      in_row += w < wave ? c : 0;
+      row_total += c;
+    }
+    const u64 s = base + (u64) j * kBlock + tid;
+    const u64 started = rec0 + before + in_row + (u32) __popcll(starts[j] & upto);
+    bool keep = false;
+    if (s < nflat && started > 0) {
+      const u64 rec = started - 1;
+      keep = rec < rec_len && ((rec_bits[rec >> 3] >> (rec & 7)) & 1);
+    }
+    const u64 m = __ballot(keep);
+    if (lane == 0) row_bits[tile * (kDecodeTile / 64) + j * kWaves + wave] = m;
+    before += row_total;
+  }
+}
+
 // ---- nested scans over sibling repeated groups ---------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_record_starts(const u8* levels, const u64* tile_offsets,
                                                           u64 nslots, u64* starts, u64 max_starts) {
@@ -2416,6 +2467,16 @@ hipError_t launch_lsm_insert(const LsmArgs& a, hipStream_t s) {
 hipError_t launch_lsm_filter(const LsmArgs& a, hipStream_t s) {
   if (a.nrows == 0) return hipSuccess;
   hipLaunchKernelGGL(k_lsm_filter, dim3(grid_for(a.nrows)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_filter_expand(const uint8_t* levels, const uint64_t* rec_offsets, uint64_t nflat,
+                                const uint8_t* rec_bits, uint64_t rec_len, uint64_t* row_bits,
+                                hipStream_t s) {
+  const u64 ntiles = (nflat + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_filter_expand, dim3((unsigned) ntiles), dim3(kBlock), 0, s, levels,
+                     (const u64*) rec_offsets, (u64) nflat, rec_bits, (u64) rec_len, (u64*) row_bits);
   return hipGetLastError();
 }
 

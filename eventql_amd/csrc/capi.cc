@@ -587,11 +587,9 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch, const evql_pl
   if (plan->row_filter_bits || plan->row_begin || plan->row_end) {
     return fail(EVQL_EARG, "a chain scan takes its row filters from the chain");
   }
-  if (tables.size() > 1 && plan->scan_mode != EVQL_SCAN_FLAT) {
-    // PartitionCursor builds CSTableScan for aggregating statements (partition_cursor.cc:
-    // 205-213); its setFilter is not lowered
-    return fail(EVQL_ENOTSUP, "nested scan over a chain of tables");
-  }
+  // (PartitionCursor builds one CSTableScan per file for aggregating statements and calls
+  // setFilter on it, partition_cursor.cc:205-213: a nested plan takes the chain's record
+  // bits like a flat one, query_prepare expands them to flattened rows)
   if (tables.size() > 1 && plan->n_select == 0 && plan->n_group == 0) {
     return fail(EVQL_ENOTSUP, "bare scan over a chain of tables");
   }
@@ -726,7 +724,8 @@ int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out) {
   }
   // scaled to the scanned row range; + result bytes (key + 8 B per aggregate)
   const uint64_t nrows = q->table->layout.num_rows;
-  if (nrows && q->stats.rows_scanned != nrows && q->chain.empty()) {
+  if (nrows && q->stats.rows_scanned != nrows && q->chain.empty() &&
+      q->reported_rows_scanned == ~0ull) {
     bytes = uint64_t(double(bytes) * double(q->stats.rows_scanned) / double(nrows));
   }
   for (const evql_query* part : q->chain) {  // (chain_merge summed the row counters)

@@ -998,7 +998,15 @@ Status chain_merge(evql_query* head) {
       rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
       rc[c].mode = ca.mode;
       rc[c].bits = ca.bits;
-      if (ca.packed) {
+      if (q->nested) {
+        // first rows of a nested scan are FLATTENED rows: the operator's own columns
+        // (fetch_results gathers from the same sources)
+        if (ca.packed) {
+          rc[c].pages = q->nested_packed[c].pages;
+          rc[c].base = q->nested_packed[c].base;
+        }
+        rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
+      } else if (ca.packed) {
         const MaterializedColumn& m = t->materialized[ca.name];
         rc[c].pages = m.d_packed_pages;
         rc[c].base = m.d_packed;

@@ -281,7 +281,6 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
   if (within && plan->n_scan_select == 0) {
     return Status::error(EVQL_EARG, "WITHIN RECORD scan without a scan select list");
   }
-  if (nested && plan->row_filter_bits) return unsup("row filter on a nested scan");
   if (nested && (plan->row_begin || plan->row_end)) return unsup("row range on a nested scan");
   if (plan->n_scan_columns > EVQL_MAX_COLS_HOST) return unsup("too many scan columns");
   if (plan->n_select == 0) return unsup("bare scans are not lowered (no GROUP BY / aggregate)");

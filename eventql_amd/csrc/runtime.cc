@@ -1251,6 +1251,8 @@ static Status materialize_within_record(evql_query* q) {
   hipEventDestroy(e0);
   hipEventDestroy(e1);
   q->nested_rows = nrec;
+  // (the reference counts the flattened rows it read, not the records it emitted)
+  q->reported_rows_scanned = nflat;
   return Status();
 }
 
@@ -1469,9 +1471,50 @@ static Status compile_plan_kernels(evql_query* q);
 
 static Status apply_where_resets(evql_query* q, const evql_table::LeafLevels& leaf);
 
+// Row filter of a nested scan.  CSTableScan reads filter_[record] when a record starts and
+// every flattened row of a rejected record fails where_pred (CSTableScan.cc:426, 642-645):
+// a record mask.  The fused kernel tests one bit per row of ITS input:
+//  * WITHIN RECORD, scans without columns, leaves that are not repeated: a row is a
+//    record, the caller's bits are the row filter as they are;
+//  * otherwise the record bits are expanded once, here, to one bit per leaf slot
+//    (k_filter_expand); the expansion belongs to the query and replaces d_row_filter.
+// The statistics follow the reference's counters: its nested loop counts every flattened
+// row as scanned, its column-less loop only the records the filter keeps.
+static Status expand_record_filter(evql_query* q, const evql_table::LeafLevels& leaf) {
+  hipStream_t s = q->ctx->stream;
+  const uint64_t nrec = q->table->layout.num_rows;
+  if (q->kp.cols.empty() && !q->within_record) {
+    std::vector<uint8_t> bits = q->row_filter_host;
+    const uint64_t len = std::min<uint64_t>(q->row_filter_len, nrec);
+    if (bits.empty()) {  // a chain's filter lives on the device
+      bits.resize((len + 7) / 8);
+      if (len) HIP_TRY(hipMemcpy(bits.data(), q->d_row_filter, bits.size(), hipMemcpyDeviceToHost));
+    }
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < len; ++r) kept += (bits[r >> 3] >> (r & 7)) & 1;
+    q->reported_rows_scanned = kept;
+  }
+  if (q->within_record || !leaf.levels) return Status();
+  const uint64_t nflat = q->nested_rows;
+  const uint64_t ntiles = (nflat + kDecodeTile - 1) / kDecodeTile;
+  DevBuf<uint64_t> d_rows;
+  HIP_TRY(d_rows.alloc((ntiles * (kDecodeTile / 64) + 2) * 8));
+  HIP_TRY(launch_filter_expand(leaf.levels, leaf.rec_offsets, nflat, q->d_row_filter,
+                               std::min<uint64_t>(q->row_filter_len, nrec), d_rows, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (q->row_filter_owned) hipFree(q->d_row_filter);
+  q->d_row_filter = reinterpret_cast<uint8_t*>(d_rows.release());
+  q->row_filter_owned = true;
+  q->row_filter_len = nflat;
+  return Status();
+}
+
 Status query_prepare(evql_query* q) {
   evql_table* t = q->table;
   evql_table::LeafLevels where_leaf;
+  // a row filter on a nested scan holds one bit per RECORD (setFilter, CSTableScan.cc:
+  // 203-204): its expansion to flattened rows needs the leaf's levels as well
+  const bool record_filter = q->nested && (q->d_row_filter || !q->row_filter_host.empty());
   if (q->within_record) {
     Status st = materialize_within_record(q);
     if (!st.ok()) return st;
@@ -1479,7 +1522,8 @@ Status query_prepare(evql_query* q) {
     Status st;
     if (!q->nested_siblings) {
       st = materialize_nested(q, q->kp.cols, &q->nested_flat, &q->nested_rows,
-                              q->nested_where_mixed ? &where_leaf : nullptr, &q->nested_strpos);
+                              q->nested_where_mixed || record_filter ? &where_leaf : nullptr,
+                              &q->nested_strpos);
       // (the planner's chain check reads names only: groups that merely look like one
       // chain are caught by the slot counts)
       if (!st.ok() && st.code == EVQL_ENOTSUP && !q->nested_where_mixed &&
@@ -1488,6 +1532,10 @@ Status query_prepare(evql_query* q) {
       } else if (!st.ok()) {
         return st;
       }
+    }
+    if (q->nested_siblings && record_filter) {
+      // (the rows of a record come from k_zip_rows' row offsets, which are not kept)
+      return Status::error(EVQL_ENOTSUP, "record filter over sibling repeated groups is not lowered");
     }
     if (q->nested_siblings) {
       st = materialize_nested_zip(q, q->kp.cols, &q->nested_flat, &q->nested_rows, &q->nested_strpos);
@@ -1589,17 +1637,22 @@ Status query_prepare(evql_query* q) {
   // 0.36 -> 0.58 ms)
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_status), 16));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_counters), 64));
-  if (q->nested_where_mixed) {
-    st = apply_where_resets(q, where_leaf);
-    if (!st.ok()) return st;
-  }
-  HIP_TRY(hipEventCreate(&q->ev0));
-  HIP_TRY(hipEventCreate(&q->ev1));
   if (!q->row_filter_host.empty()) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_row_filter), q->row_filter_host.size() + 16));
     HIP_TRY(hipMemcpy(q->d_row_filter, q->row_filter_host.data(), q->row_filter_host.size(),
                       hipMemcpyHostToDevice));
   }
+  if (record_filter) {
+    st = expand_record_filter(q, where_leaf);
+    if (!st.ok()) return st;
+  }
+  if (q->nested_where_mixed) {
+    // (evql_where_rows reads the row filter: the expanded one must be in place)
+    st = apply_where_resets(q, where_leaf);
+    if (!st.ok()) return st;
+  }
+  HIP_TRY(hipEventCreate(&q->ev0));
+  HIP_TRY(hipEventCreate(&q->ev1));
   return Status();
 }
 
@@ -2191,6 +2244,7 @@ Status query_finish(evql_query* q) {
     uint64_t counters[8];
     HIP_TRY(hipMemcpy(counters, q->d_counters, 64, hipMemcpyDeviceToHost));
     q->stats.rows_passed = counters[0];
+    if (q->reported_rows_scanned != ~0ull) q->stats.rows_scanned = q->reported_rows_scanned;
     q->stats.used_lds_table = q->kp.lds_slots > 0;
     q->launched = false;
     // the groups stay in HBM; they are compacted and copied to the host only

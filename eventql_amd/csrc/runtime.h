@@ -250,6 +250,9 @@ struct evql_query {
   uint64_t row_filter_len = 0;
   uint8_t* d_row_filter = nullptr;
   bool row_filter_owned = true;  // false: the bits belong to an evql_lsm_chain
+  // nested scans: one bit per record on entry; query_prepare replaces it by its expansion to
+  // one bit per flattened row where the two differ (runtime.cc expand_record_filter)
+  uint64_t reported_rows_scanned = ~0ull;  // != ~0: the reference's count, where it is not the row range
   // evql_query_create_chain: this query scans the first table of a partition's chain;
   // `chain` holds the queries of the tables behind it (owned).  After execute their
   // groups are merged in chain order into d_mtab (exchange.cc chain_merge).

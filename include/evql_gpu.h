@@ -427,9 +427,12 @@ typedef struct {
   uint32_t n_select;
 
   /* AbstractCSTableScan::setFilter (CSTableScan.h:36-41): bit i == 0 drops
-   * record i.  NULL => no external filter */
+   * record i.  NULL => no external filter.  One bit per RECORD in every scan mode: a
+   * nested scan drops all flattened rows of a record whose bit is 0 (CSTableScan.cc:426,
+   * 642-645), a WITHIN RECORD scan emits no row for it; records behind row_filter_len are
+   * dropped.  (EVQL_ENOTSUP: a filtered nested scan over sibling repeated groups.) */
   const uint8_t* row_filter_bits;
-  uint64_t row_filter_len; /* in rows */
+  uint64_t row_filter_len; /* in records */
 
   uint32_t group_mode; /* evql_group_mode */
   uint32_t scan_mode;  /* evql_scan_mode  */
@@ -758,8 +761,11 @@ int evql_lsm_chain_filter(evql_lsm_chain_t* ch, int idx,
  * row in scan order (groupby.cc:161-172) and count_distinct counts the union of the
  * tables' sets.  `ch` must be built and outlive the query; every other entry point
  * (execute, next_batch, set_order, stats ...) takes the returned query as usual.
- * EVQL_SCAN_FLAT only (PartitionCursor builds FastCSTableScan for NO_AGGREGATION
- * statements, :197-204; anything else answers EVQL_ENOTSUP).
+ * Every scan mode: PartitionCursor builds FastCSTableScan for NO_AGGREGATION statements
+ * (EVQL_SCAN_FLAT) and CSTableScan for the others (EVQL_SCAN_NESTED[_WITHIN_RECORD]),
+ * :42-50, 197-217, and calls setFilter on either; the chain's filters hold one bit per
+ * record.  EVQL_ENOTSUP: a bare scan over more than one table, and whatever
+ * evql_query_create refuses for one table under a row filter.
  */
 int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch,
                             const evql_plan_desc_t* plan, evql_query_t** out);

@@ -115,12 +115,14 @@ class GpuGroupByScan : public TableExpression {
   GpuGroupByScan(evql_ctx_t* ctx, evql_table_t* table, const evql_plan_desc_t& plan,
                  Heartbeat heartbeat = nullptr)
       : query_(nullptr), heartbeat_(std::move(heartbeat)) {
-    int rc = evql_query_create(ctx, table, &plan, &query_);
-    if (rc == EVQL_ENOTSUP) throw NotLowerable(evql_last_error());
-    if (rc != EVQL_OK) throw std::runtime_error(evql_last_error());
-    const int n = evql_query_column_count(query_);
-    for (int i = 0; i < n; ++i) types_.push_back(SType(evql_query_column_type(query_, i)));
-    bufs_.resize(types_.size());
+    created(evql_query_create(ctx, table, &plan, &query_));
+  }
+  // over the file chain of a partition (GroupByExpression over PartitionCursor): flat,
+  // nested and WITHIN RECORD plans, the row filters come from the chain
+  GpuGroupByScan(evql_ctx_t* ctx, evql_lsm_chain_t* chain, const evql_plan_desc_t& plan,
+                 Heartbeat heartbeat = nullptr)
+      : query_(nullptr), heartbeat_(std::move(heartbeat)) {
+    created(evql_query_create_chain(ctx, chain, &plan, &query_));
   }
   ~GpuGroupByScan() override { evql_query_destroy(query_); }
   GpuGroupByScan(const GpuGroupByScan&) = delete;
@@ -161,6 +163,13 @@ class GpuGroupByScan : public TableExpression {
   }
 
  private:
+  void created(int rc) {
+    if (rc == EVQL_ENOTSUP) throw NotLowerable(evql_last_error());
+    if (rc != EVQL_OK) throw std::runtime_error(evql_last_error());
+    const int n = evql_query_column_count(query_);
+    for (int i = 0; i < n; ++i) types_.push_back(SType(evql_query_column_type(query_, i)));
+    bufs_.resize(types_.size());
+  }
   static int heartbeat_thunk(void* self) {
     auto* s = static_cast<GpuGroupByScan*>(self);
     return s->heartbeat_().isSuccess() ? 0 : 1;
