@@ -8,26 +8,12 @@
 #include "sha1.h"
 
 namespace evql {
-const std::string& last_error();
-void set_cache_dir(const std::string& d);
-Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache);
-Status table_from_image(evql_ctx* ctx, const void* image, size_t len, bool keep_host,
-                        evql_table** out);
-Status query_prepare(evql_query* q);
-Status query_launch(evql_query* q);
-Status query_finish(evql_query* q);
-Status query_reset(evql_query* q);
-Status query_recount(evql_query* q);
-Status query_dense_into_table(evql_query* q);
-Status chain_merge(evql_query* head);  // exchange.cc
-size_t lsm_chain_parts(const evql_lsm_chain* ch, std::vector<evql_table*>* tables,
-                       std::vector<const uint8_t*>* d_filters);  // lsm.cc
-evql_ctx* lsm_chain_ctx(const evql_lsm_chain* ch);
-Status query_reserve_groups(evql_query* q, uint64_t extra);
-Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, uint64_t n);
-Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,
-                       uint64_t offset);
-Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
+static thread_local std::string g_last_error;
+void set_last_error(const std::string& m) { g_last_error = m; }
+int fail(int code, const std::string& m) {
+  g_last_error = m;
+  return code;
+}
 }  // namespace evql
 
 using namespace evql;
@@ -73,7 +59,7 @@ static int writer_put(evql_writer_t* w, int col, uint64_t n, const uint64_t* rlv
 
 extern "C" {
 
-const char* evql_last_error(void) { return last_error().c_str(); }
+const char* evql_last_error(void) { return g_last_error.c_str(); }
 const char* evql_version(void) { return "eventql_amd 0.1 (gfx950)"; }
 
 // ---- context -----------------------------------------------------------------------

@@ -43,7 +43,7 @@ struct AggPlan {
   // bits) of multiples of a quantum; index into EvqlArgs::fscale / fbound
   int exact_index = -1;
   // partitioned path: the argument is an unsigned value known to stay below 2^32 - 1
-  // (column statistics, runtime.cc choose_tuple_widths); it travels as 32 bits
+  // (column statistics, value_bounds.cc choose_tuple_widths); it travels as 32 bits
   bool narrow_arg = false;
 };
 

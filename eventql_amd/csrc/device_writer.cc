@@ -40,14 +40,6 @@
 
 namespace evql {
 
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      return Status::error(EVQL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    }                                                                              \
-  } while (0)
-
 namespace {
 struct ColumnWork {
   uint64_t nslots = 0;              // level-stream length (= rows for flat columns)

@@ -17,18 +17,6 @@
 
 using namespace evql;
 
-namespace evql {
-Status query_dense_into_table(evql_query* q);
-}
-
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      return Status::error(EVQL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    }                                                                                       \
-  } while (0)
-
 // ---------------------------------------------------------------------------------------
 // in-process hub: ranks are threads of one process
 // ---------------------------------------------------------------------------------------

@@ -22,14 +22,6 @@
 
 using namespace evql;
 
-#define LSM_HIP(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e__ = (expr);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      return Status::error(EVQL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    }                                                                                    \
-  } while (0)
-
 struct evql_lsm_chain {
   evql_ctx* ctx = nullptr;
   struct Entry {
@@ -67,10 +59,10 @@ Status build(evql_lsm_chain* ch) {
   uint64_t cap = 1024;
   while (cap < 2 * total) cap <<= 1;
   DevBuf<uint64_t> d_tab, d_counters;
-  LSM_HIP(d_tab.alloc(cap * 4 * 8));
-  LSM_HIP(d_counters.alloc(32));
-  LSM_HIP(hipMemsetAsync(d_tab, 0xff, cap * 4 * 8, s));
-  LSM_HIP(hipMemsetAsync(d_counters, 0, 32, s));
+  HIP_TRY(d_tab.alloc(cap * 4 * 8));
+  HIP_TRY(d_counters.alloc(32));
+  HIP_TRY(hipMemsetAsync(d_tab, 0xff, cap * 4 * 8, s));
+  HIP_TRY(hipMemsetAsync(d_counters, 0, 32, s));
 
   const size_t n = ch->entries.size();
   std::vector<LsmArgs> args(n);
@@ -113,20 +105,20 @@ Status build(evql_lsm_chain* ch) {
       a.has_skip = 1;
     }
     if (e.is_arena) {
-      LSM_HIP(d_skips[i].alloc(e.arena_skip.size()));
-      LSM_HIP(hipMemcpyAsync(d_skips[i], e.arena_skip.data(), e.arena_skip.size(),
+      HIP_TRY(d_skips[i].alloc(e.arena_skip.size()));
+      HIP_TRY(hipMemcpyAsync(d_skips[i], e.arena_skip.data(), e.arena_skip.size(),
                              hipMemcpyHostToDevice, s));
       a.arena_skip = d_skips[i];
     }
     const uint64_t nwords = (a.nrows + 63) / 64;
-    LSM_HIP(hipMalloc(reinterpret_cast<void**>(&e.d_bits), (nwords ? nwords : 1) * 8 + 16));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e.d_bits), (nwords ? nwords : 1) * 8 + 16));
     a.bits = e.d_bits;
-    LSM_HIP(launch_lsm_insert(a, s));
+    HIP_TRY(launch_lsm_insert(a, s));
     if (id_set_empty && i + 1 < n) {
       // (only the emptiness of the id set feeds back into the next table's decision)
       uint64_t counters[4] = {0, 0, 0, 0};
-      LSM_HIP(hipMemcpyAsync(counters, d_counters, 32, hipMemcpyDeviceToHost, s));
-      LSM_HIP(hipStreamSynchronize(s));
+      HIP_TRY(hipMemcpyAsync(counters, d_counters, 32, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
       if (counters[1]) return Status::error(EVQL_ERUNTIME, "invalid SHA1Hash");  // util/SHA1.cc:79-85
       id_set_empty = counters[2] == 0;
     }
@@ -136,15 +128,15 @@ Status build(evql_lsm_chain* ch) {
   for (size_t i = 0; i < n; ++i) {
     evql_lsm_chain::Entry& e = ch->entries[i];
     if (!e.needs_filter) continue;
-    LSM_HIP(launch_lsm_filter(args[i], s));
+    HIP_TRY(launch_lsm_filter(args[i], s));
     uint64_t counters[4] = {0, 0, 0, 0};
-    LSM_HIP(hipMemcpyAsync(counters, d_counters, 32, hipMemcpyDeviceToHost, s));
-    LSM_HIP(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(counters, d_counters, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     if (counters[1]) return Status::error(EVQL_ERUNTIME, "invalid SHA1Hash");  // util/SHA1.cc:79-85
     e.kept = counters[0] - prev_kept;
     prev_kept = counters[0];
   }
-  LSM_HIP(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(s));
   return Status();
 }
 

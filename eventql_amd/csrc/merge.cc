@@ -85,7 +85,7 @@ struct evql_merge {
 
 namespace {
 
-// instance_loadstate, inverse of save_state() in runtime.cc
+// instance_loadstate, inverse of save_state() in results.cc
 bool load_state(uint32_t fn, Reader* r, Cell* c) {
   switch (fn) {
     case EVQL_AGG_COUNT:

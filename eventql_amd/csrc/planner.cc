@@ -413,7 +413,7 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
         if (below && other.rlevel_max < bound) bound = other.rlevel_max;
       }
       if (bound < cl.rlevel_max) {
-        // sibling repeated groups: zipped level by level (runtime.cc materialize_nested_zip);
+        // sibling repeated groups: zipped level by level (nested.cc materialize_nested_zip);
         // the record scan's per-record reduction assumes one chain
         if (within) {
           return unsup("nested columns from different repeated groups in a record scan: " + cl.name +

@@ -1,0 +1,1013 @@
+// results.cc -- groups leaving the device: fetch, ORDER BY .. LIMIT, and emission as
+// SVector columns (on the device for large results, on the host otherwise).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include "runtime.h"
+#include "sha1.h"
+
+namespace evql {
+
+// ---------------------------------------------------------------------------
+// large results: the output columns packed on the device
+// ---------------------------------------------------------------------------
+// GroupByExpression::nextBatch (groupby.cc:187-220) runs `method_call` of every select
+// expression per group and appends the value to the column's SVector.  For 1e7 groups the
+// host loop (record copy, sort, one eval_expr per cell) took seconds.  When every select
+// expression is the group key, a bare aggregate or the first-row value of a scan column --
+// config 4 / 4s, and what `select k, count(1), sum(x) .. group by k` looks like -- one
+// kernel writes the packed SVector bytes (svalue.cc:410-517) of every column for ALL groups;
+// the host copies each column once into pinned memory and next_batch hands out slices.
+// Row order is unspecified for a GROUP BY; small results keep the host path
+// and its deterministic order.
+static const uint64_t kDeviceEmitMinGroups = 1 << 16;
+
+static bool device_emit_columns(const evql_query* q, bool merged, EmitArgs* ea) {
+  const KernelPlan& kp = q->rplan();
+  const size_t nsel = q->select.size();
+  if (q->group_mode != EVQL_MODE_FINAL || !q->order.empty() || q->has_limit) return false;
+  if (nsel == 0 || nsel > kMaxEmitCols) return false;
+  for (size_t i = 0; i < nsel; ++i) {
+    const LoweredProgram& lp = q->select[i];
+    EmitCol& e = ea->col[i];
+    e = EmitCol{};
+    e.count_word = -1;
+    e.stype = lp.return_type;
+    e.elem = lp.return_type == EVQL_T_BOOL ? 2 : 9;
+    if (lp.return_type == EVQL_T_NIL) return false;
+    if (lp.is_aggregate) {
+      if (lp.call->kind != Expr::AGG_GET) return false;  // post-aggregate arithmetic: host
+      const AggPlan& a = kp.aggs[q->select_agg_index[i]];
+      if (a.exact_index >= 0) return false;  // (128-bit rounding of an exact sum: host)
+      e.kind = 1;
+      e.word = uint32_t(1 + kp.state_word_base() + a.first_word);
+      switch (a.fn) {
+        case EVQL_AGG_COUNT: case EVQL_AGG_SUM_UINT64: case EVQL_AGG_SUM_INT64:
+        case EVQL_AGG_SUM_FLOAT64: case EVQL_AGG_COUNT_DISTINCT_UINT64:
+          break;
+        case EVQL_AGG_MEAN_UINT64: case EVQL_AGG_MEAN_INT64: case EVQL_AGG_MEAN_FLOAT64:
+          e.is_mean = 1;
+          e.count_word = int32_t(e.word + 1);
+          break;
+        default:  // min / max
+          e.count_word = int32_t(e.word + 1);
+      }
+    } else if (q->select_passthrough[i]) {
+      if (lp.return_type == EVQL_T_STRING) return false;
+      e.kind = 0;
+    } else {
+      // a bare column: select expr = X_INPUT(j) of the scan select list = X_INPUT(c)
+      if (merged || !kp.need_first_row || lp.call->kind != Expr::INPUT) return false;
+      const uint32_t j = lp.call->input;
+      if (j >= q->scan_select.size() || q->scan_select[j].call->kind != Expr::INPUT) return false;
+      const uint32_t c = q->scan_select[j].call->input;
+      if (c >= kp.cols.size() || q->nested) return false;
+      const ColAccess& ca = kp.cols[c];
+      if (ca.stype != lp.return_type) return false;
+      e.kind = 2;
+      e.src = c;
+      e.to_float = ca.stype == EVQL_T_FLOAT64 && ca.from_uint_to_float;
+      if (ca.string_hash) e.elem = 0;
+    }
+  }
+  ea->ncols = uint32_t(nsel);
+  return true;
+}
+
+static Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap && *p) return Status();
+  if (*p) hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = bytes + bytes / 8 + 4096;
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(p), want, hipHostMallocDefault));
+  *cap = want;
+  return Status();
+}
+
+static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec, uint64_t n,
+                             uint32_t nwords) {
+  evql_table* t = q->table;
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = q->ctx->stream;
+  const uint32_t nsel = ea.ncols;
+  evql_query::DeviceEmit& de = q->demit;
+  de.col.resize(nsel, nullptr);
+  de.col_cap.resize(nsel, 0);
+  de.off.resize(nsel, nullptr);
+  de.off_cap.resize(nsel, 0);
+  de.elem.assign(nsel, 0);
+  ea.records = d_rec;
+  ea.n = n;
+  ea.rw = nwords + 1;
+  ea.image = t->d_image;
+  bool need_first = false;
+  for (uint32_t i = 0; i < nsel; ++i) need_first = need_first || ea.col[i].kind == 2;
+  DevBuf<uint64_t> d_rows, d_vals;
+  DevBuf<uint8_t> d_tags;
+  DevBuf<RtColumn> d_cols;
+  const uint32_t nc = uint32_t(kp.cols.size());
+  if (need_first) {
+    // the column values of every group's first row (strings: their strpos words)
+    std::vector<RtColumn> rc(nc);
+    for (uint32_t c = 0; c < nc; ++c) {
+      const ColAccess& ca = kp.cols[c];
+      rc[c] = RtColumn{};
+      rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
+      rc[c].mode = ca.mode;
+      rc[c].bits = ca.bits;
+      if (ca.packed) {
+        const MaterializedColumn& m = t->materialized[ca.name];
+        rc[c].pages = m.d_packed_pages;
+        rc[c].base = m.d_packed;
+      } else if (ca.mode == ColAccess::SOA) {
+        const MaterializedColumn& m = t->materialized[ca.name];
+        rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
+        rc[c].tags = m.d_tags;
+      }
+    }
+    HIP_TRY(d_rows.alloc(n * 8));
+    HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
+    HIP_TRY(d_vals.alloc(n * nc * 8));
+    HIP_TRY(d_tags.alloc(n * nc));
+    HIP_TRY(launch_extract_word(d_rec, n, nwords + 1, uint32_t(1 + kp.first_row_word()), d_rows, s));
+    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (rc lives until here)
+    ea.first_vals = d_vals;
+    ea.first_tags = d_tags;
+  }
+  // device buffers of the packed columns
+  std::vector<DevBuf<uint8_t>> d_out(nsel);
+  std::vector<DevBuf<uint64_t>> d_off(nsel);
+  std::vector<uint64_t> str_bytes(nsel, 0);
+  DevBuf<EmitArgs> d_args;
+  HIP_TRY(d_args.alloc(sizeof(EmitArgs)));
+  for (uint32_t i = 0; i < nsel; ++i) {
+    EmitCol& e = ea.col[i];
+    de.elem[i] = e.elem;
+    if (e.elem) {
+      HIP_TRY(d_out[i].alloc(n * e.elem));
+      e.out = d_out[i];
+    } else {
+      e.pages = t->d_pages[kp.cols[e.src].layout_index][0];
+      HIP_TRY(d_off[i].alloc((n + 2) * 8));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_emit_fixed(d_args, n, s));
+  bool strings = false;
+  for (uint32_t i = 0; i < nsel; ++i) {
+    if (ea.col[i].elem) continue;
+    strings = true;
+    HIP_TRY(launch_emit_str_sizes(d_args, i, n, d_off[i], s));
+    HIP_TRY(launch_exclusive_scan(d_off[i], n, d_off[i].p + n, s));
+    HIP_TRY(hipMemcpyAsync(&str_bytes[i], d_off[i].p + n, 8, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (strings) {
+    for (uint32_t i = 0; i < nsel; ++i) {
+      if (ea.col[i].elem) continue;
+      HIP_TRY(d_out[i].alloc(str_bytes[i] + 16));
+      ea.col[i].out = d_out[i];
+      ea.col[i].offsets = d_off[i];
+    }
+    HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
+    for (uint32_t i = 0; i < nsel; ++i) {
+      if (!ea.col[i].elem) HIP_TRY(launch_emit_str_bytes(d_args, i, n, s));
+    }
+  }
+  // one copy per column into pinned host memory
+  for (uint32_t i = 0; i < nsel; ++i) {
+    const size_t bytes = ea.col[i].elem ? size_t(n) * ea.col[i].elem : size_t(str_bytes[i]);
+    Status st = pinned_reserve(&de.col[i], &de.col_cap[i], bytes);
+    if (!st.ok()) return st;
+    if (bytes) HIP_TRY(hipMemcpyAsync(de.col[i], d_out[i], bytes, hipMemcpyDeviceToHost, s));
+    if (!ea.col[i].elem) {
+      uint8_t* po = reinterpret_cast<uint8_t*>(de.off[i]);
+      st = pinned_reserve(&po, &de.off_cap[i], (n + 1) * 8);
+      de.off[i] = reinterpret_cast<uint64_t*>(po);
+      if (!st.ok()) return st;
+      HIP_TRY(hipMemcpyAsync(de.off[i], d_off[i], (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  de.active = true;
+  return Status();
+}
+
+// the groups as dense device records [kind, slot words...] on their way to the host
+struct FetchedRecords {
+  uint32_t nwords = 0;        // slot words of a record
+  uint64_t* d_rec = nullptr;  // borrowed (small buffer, merged dense records) or `own`
+  DevBuf<uint64_t> own;       // records that do not fit the small buffer
+  uint64_t n = 0;
+  uint64_t total = 0;         // groups of the result before LIMIT
+};
+
+// step 1: the dense records of the partitioned path and the compacted slots of the group
+// table (after an exchange: of the merged table) in one buffer
+static Status collect_records(evql_query* q, FetchedRecords* r) {
+  evql_ctx* ctx = q->ctx;
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = ctx->stream;
+  // after an exchange the groups live in the merged table (wider slots)
+  const bool merged = q->merged;
+  r->nwords = merged ? q->m_words : uint32_t(kp.words_per_slot());
+  uint64_t* const gtab = merged ? q->d_mtab : q->d_gtab;
+  const uint64_t gcap = merged ? (q->merged_dense ? q->mdense_n : q->mcap) : q->gcap;
+  const uint64_t stride = gcap + 8;
+  const uint64_t maxrec = gcap + 2;
+  RecordsView view;
+  if (!merged) {
+    Status stv = query_records_view(q, &view);
+    if (!stv.ok()) return stv;
+  }
+  const uint64_t dense_n = merged ? 0 : view.nd;
+  uint64_t* d_cnt = q->d_counters + 5;
+  // the record buffer is sized by the number of groups (counted by finish /
+  // recount / reset), not by the table capacity
+  r->n = q->stats.num_groups;
+  if (r->n > maxrec + dense_n) r->n = maxrec + dense_n;
+  r->total = r->n;
+  // small results (the usual case) reuse a per-query 1 MiB buffer: no allocation
+  // inside a step
+  const size_t kSmallRec = 1 << 20;
+  if (r->n && merged && q->merged_dense) {
+    // (a bucketed merge left the groups as dense records already)
+    r->n = std::min(r->n, q->mdense_n);
+    r->d_rec = q->d_mdense;
+  } else if (r->n) {
+    if (r->n * (r->nwords + 1) * 8 <= kSmallRec) {
+      if (!q->d_small_rec) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_small_rec), kSmallRec));
+      r->d_rec = q->d_small_rec;
+    } else {
+      HIP_TRY(r->own.alloc(r->n * (r->nwords + 1) * 8));
+      r->d_rec = r->own;
+    }
+    // dense records of the partitioned path first, the table's groups behind them
+    const uint64_t nd = std::min(dense_n, r->n);
+    if (nd) {
+      HIP_TRY(hipMemcpyAsync(r->d_rec, view.dense, nd * (r->nwords + 1) * 8, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+    if (r->n > nd) {
+      HIP_TRY(launch_table_compact(gtab, gcap, stride, r->nwords, r->d_rec + nd * (r->nwords + 1),
+                                   r->n - nd, d_cnt, s));
+    }
+  }
+  return Status();
+}
+
+// step 2, ORDER BY .. LIMIT asking for fewer rows than there are groups: only the
+// want = offset + limit smallest records by the first sort key (plus, with further sort
+// keys, every tie of the boundary key) leave the device: radix select over the dense
+// records, 8 bits per pass
+static Status select_top_records(evql_query* q, uint64_t want, FetchedRecords* r) {
+  hipStream_t s = q->ctx->stream;
+  uint64_t m = 0;
+  if (want > 0) {
+    DevBuf<uint64_t> d_keys, d_hist, d_idx, d_ctr;
+    HIP_TRY(d_keys.alloc(r->n * 8));
+    HIP_TRY(d_hist.alloc(256 * 8));
+    HIP_TRY(d_idx.alloc(r->n * 8));
+    HIP_TRY(d_ctr.alloc(3 * 8));
+    OrderKeyArgs ka = q->order_key;
+    ka.records = r->d_rec;
+    ka.record_words = r->nwords + 1;
+    ka.n = r->n;
+    ka.keys = d_keys;
+    HIP_TRY(launch_order_keys(ka, s));
+    uint64_t hi_mask = 0, hi_value = 0, remaining = want;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      uint64_t hist[256];
+      HIP_TRY(hipMemsetAsync(d_hist, 0, sizeof(hist), s));
+      HIP_TRY(launch_radix_hist(d_keys, r->n, hi_mask, hi_value, uint32_t(shift), d_hist, s));
+      HIP_TRY(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      uint64_t d = 0;
+      while (d < 255 && hist[d] < remaining) remaining -= hist[d++];
+      hi_value |= d << shift;
+      hi_mask |= 0xFFull << shift;
+    }
+    // `remaining` = how many records with key == hi_value the result needs
+    const uint64_t max_eq = q->order.size() == 1 ? remaining : r->n;
+    uint64_t ctr[3] = {0, 0, 0};
+    HIP_TRY(hipMemsetAsync(d_ctr, 0, sizeof(ctr), s));
+    HIP_TRY(launch_order_collect(d_keys, r->n, hi_value, max_eq, d_idx, d_ctr, s));
+    HIP_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    m = ctr[2];
+    DevBuf<uint64_t> d_rec2;
+    HIP_TRY(d_rec2.alloc(m * (r->nwords + 1) * 8));
+    HIP_TRY(launch_gather_records(r->d_rec, r->nwords + 1, d_idx, m, d_rec2, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    r->own = std::move(d_rec2);
+    r->d_rec = r->own;
+  }
+  r->n = m;
+  return Status();
+}
+
+// step 3: the records on the host in a deterministic order: by first row (scan order) or
+// by identity
+static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t nwords) {
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = q->ctx->stream;
+  q->records.assign(n * (nwords + 1), 0);
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(q->records.data(), d_rec, n * (nwords + 1) * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  const size_t rw = nwords + 1;
+  std::vector<uint64_t> idx(n);
+  for (uint64_t i = 0; i < n; ++i) idx[i] = i;
+  const size_t keyw = kp.need_first_row ? size_t(1 + kp.first_row_word()) : 1;
+  const uint64_t* r = q->records.data();
+  std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+    const uint64_t ka = r[a * rw + keyw], kb = r[b * rw + keyw];
+    if (ka != kb) return ka < kb;
+    return r[a * rw] < r[b * rw];
+  });
+  std::vector<uint64_t> sorted(q->records.size());
+  for (uint64_t i = 0; i < n; ++i) {
+    memcpy(&sorted[i * rw], &r[idx[i] * rw], rw * 8);
+  }
+  q->records.swap(sorted);
+  return Status();
+}
+
+// step 4a, after an exchange: the first-row values of every scan column out of the merged
+// records
+static Status first_rows_from_records(evql_query* q, uint64_t n, uint32_t nwords) {
+  const KernelPlan& kp = q->rplan();
+  // the merged records carry the first-row values themselves: one word per scan
+  // column, one word of NULL-tag bits; string words point into the received bytes
+  const uint32_t nc = uint32_t(kp.cols.size());
+  const size_t rw = nwords + 1, fr0 = size_t(kp.words_per_slot()) + 1;
+  q->first_vals.resize(n * nc);
+  q->first_tags.resize(n * nc);
+  q->first_str_off.assign(n * nc, 0);
+  q->first_str_heap = q->m_heap;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t* rec = &q->records[i * rw];
+    const uint64_t tags = rec[fr0 + nc];
+    for (uint32_t c = 0; c < nc; ++c) {
+      q->first_vals[uint64_t(c) * n + i] = rec[fr0 + c];
+      q->first_tags[uint64_t(c) * n + i] = uint8_t((tags >> c) & 1);
+      if (kp.cols[c].string_hash) {
+        const uint64_t off = rec[fr0 + c] & kStrOffMask;
+        if (off + (rec[fr0 + c] >> 40) > q->first_str_heap.size()) {
+          return Status::error(EVQL_ERUNTIME, "exchange: string offset outside the received bytes");
+        }
+        q->first_str_off[uint64_t(c) * n + i] = off;
+      }
+    }
+  }
+  return Status();
+}
+
+// step 4b: the first-row values of every scan column gathered from the table, and the bytes
+// of the strings among them
+static Status first_rows_from_table(evql_query* q, uint64_t n, uint32_t nwords) {
+  evql_table* t = q->table;
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = q->ctx->stream;
+  const uint32_t nc = uint32_t(kp.cols.size());
+  std::vector<uint64_t> rows(n);
+  const size_t rw = nwords + 1;
+  // (never hand an unrecorded first row to the gather: it would read far outside the table)
+  const uint64_t row_limit = q->nested ? q->nested_rows : t->layout.num_rows;
+  for (uint64_t i = 0; i < n; ++i) {
+    rows[i] = q->records[i * rw + 1 + kp.first_row_word()];
+    if (rows[i] >= row_limit) {
+      return Status::error(EVQL_ERUNTIME, "a group's first row was not recorded");
+    }
+  }
+  std::vector<RtColumn> rc(nc);
+  for (uint32_t c = 0; c < nc; ++c) {
+    const ColAccess& ca = kp.cols[c];
+    rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
+    rc[c].mode = ca.mode;
+    rc[c].bits = ca.bits;
+    if (ca.packed && q->nested) {
+      rc[c].pages = q->nested_packed[c].pages;
+      rc[c].base = q->nested_packed[c].base;
+    } else if (ca.packed) {
+      const MaterializedColumn& m = t->materialized[ca.name];
+      rc[c].pages = m.d_packed_pages;
+      rc[c].base = m.d_packed;
+    }
+    if (q->nested) {
+      rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
+    } else if (ca.mode == ColAccess::SOA) {
+      const MaterializedColumn& m = t->materialized[ca.name];
+      // strings: (len << 40 | position); their bytes are copied out below
+      rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
+      rc[c].tags = m.d_tags;
+    }
+  }
+  DevBuf<uint64_t> d_rows, d_vals;
+  DevBuf<RtColumn> d_cols;
+  DevBuf<uint8_t> d_tags;
+  HIP_TRY(d_rows.alloc(n * 8));
+  HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
+  HIP_TRY(d_vals.alloc(n * nc * 8));
+  HIP_TRY(d_tags.alloc(n * nc));
+  HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
+  q->first_vals.resize(n * nc);
+  q->first_tags.resize(n * nc);
+  HIP_TRY(hipMemcpyAsync(q->first_vals.data(), d_vals, n * nc * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(q->first_tags.data(), d_tags, n * nc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // bytes of the first-row strings: one packed heap per string column
+  q->first_str_off.assign(n * nc, 0);
+  q->first_str_heap.clear();
+  for (uint32_t c = 0; c < nc; ++c) {
+    const ColAccess& ca = kp.cols[c];
+    if (!ca.string_hash) continue;
+    std::vector<uint64_t> offs(n);
+    uint64_t total = q->first_str_heap.size();
+    const uint64_t heap0 = total;
+    for (uint64_t i = 0; i < n; ++i) {
+      offs[i] = total - heap0;
+      q->first_str_off[uint64_t(c) * n + i] = total;
+      if (!q->first_tags[uint64_t(c) * n + i]) total += q->first_vals[uint64_t(c) * n + i] >> 40;
+    }
+    const uint64_t bytes = total - heap0;
+    q->first_str_heap.resize(total);
+    if (bytes == 0) continue;
+    DevBuf<uint64_t> d_offs;
+    DevBuf<uint8_t> d_heap;
+    HIP_TRY(d_offs.alloc(n * 8));
+    HIP_TRY(d_heap.alloc(bytes));
+    HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), n * 8, hipMemcpyHostToDevice, s));
+    // (NULL rows carry strpos 0: length 0, nothing copied)
+    HIP_TRY(launch_copy_strings(t->d_image, t->d_pages[ca.layout_index][0], d_vals.p + uint64_t(c) * n,
+                                d_offs, n, d_heap, s));
+    HIP_TRY(hipMemcpyAsync(q->first_str_heap.data() + heap0, d_heap, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return Status();
+}
+
+// step 5, PARTIAL mode: the distinct values of every group and count_distinct aggregate
+static Status fetch_distinct_sets(evql_query* q, uint64_t n, uint32_t nwords) {
+  const KernelPlan& kp = q->rplan();
+  const bool merged = q->merged;
+  q->distinct_values.clear();
+  if (q->group_mode == EVQL_MODE_PARTIAL && kp.n_distinct > 0) {
+    // count_distinct's saved state is the set itself (aggregate.cc:111-117): the
+    // (group, value, flags) triples of the aggregate's pair set, grouped on the host
+    const bool hashed = kp.key_mode == KEY_HASHED;
+    q->distinct_values.resize(kp.n_distinct);
+    std::vector<uint64_t> host;
+    for (int d = 0; d < kp.n_distinct; ++d) {
+      // (merged results: the union of the ranks' / tables' sets, exchange.cc)
+      const uint64_t cap = merged ? q->mset_cap[d] : q->pairset_cap;
+      const uint64_t* d_set = merged ? q->d_mset[d] : q->d_pairset[d];
+      host.assign(cap * 3, ~0ull);
+      if (d_set && cap) HIP_TRY(hipMemcpy(host.data(), d_set, cap * 3 * 8, hipMemcpyDeviceToHost));
+      auto& sets = q->distinct_values[d];
+      for (uint64_t sl = 0; sl < cap; ++sl) {
+        uint64_t ident = host[sl], value = host[cap + sl], flags = host[2 * cap + sl];
+        if (ident == ~0ull || value == ~0ull || flags == ~0ull) continue;
+        uint64_t second;
+        if (hashed) {
+          // (a value of 2^64-1 is stored as 2^64-2 with the flags word scrambled: such
+          // a group is found under the unscrambled second identity word)
+          second = flags;
+          if (value == ~0ull - 1 && !sets.count({ident, second})) {
+            const uint64_t alt = flags ^ 0xc2b2ae3d27d4eb4full;
+            bool known = false;
+            for (uint64_t g = 0; g < n && !known; ++g) {
+              const uint64_t* rec = &q->records[g * (nwords + 1)];
+              known = rec[1] == ident && rec[2] == alt;
+            }
+            if (known) {
+              second = alt;
+              value = ~0ull;
+            }
+          }
+        } else {
+          if (flags & 2u) ident = ~0ull;
+          if (flags & 4u) value = ~0ull;
+          second = flags & 1u;  // NULL key
+        }
+        sets[{ident, second}].push_back(value);
+      }
+      for (auto& kv : sets) std::sort(kv.second.begin(), kv.second.end());
+    }
+  }
+  return Status();
+}
+
+static Status fetch_results(evql_query* q) {
+  const KernelPlan& kp = q->rplan();
+  FetchedRecords r;
+  Status st = collect_records(q, &r);
+  if (!st.ok()) return st;
+  const uint64_t want = q->offset + q->limit;
+  if (r.n && !q->order.empty() && q->has_limit && want < r.n) {
+    st = select_top_records(q, want, &r);
+    if (!st.ok()) return st;
+  }
+  const uint64_t n = r.n;
+  q->ngroups = n;
+  q->rec_stride = r.nwords + 1;
+  q->demit.active = false;
+  EmitArgs ea{};
+  if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea)) {
+    st = emit_on_device(q, ea, r.d_rec, n, r.nwords);
+    if (!st.ok()) return st;
+    q->records.clear();
+    q->distinct_values.clear();
+  } else {
+    st = records_to_host(q, r.d_rec, n, r.nwords);
+    if (!st.ok()) return st;
+    q->first_vals.clear();
+    q->first_tags.clear();
+    if (kp.need_first_row && n) {
+      st = q->merged ? first_rows_from_records(q, n, r.nwords) : first_rows_from_table(q, n, r.nwords);
+      if (!st.ok()) return st;
+    }
+    st = fetch_distinct_sets(q, n, r.nwords);
+    if (!st.ok()) return st;
+  }
+  q->stats.num_groups = r.total;
+  q->emit_pos = 0;
+  q->executed = true;
+  q->fetched = true;
+  return Status();
+}
+
+// ---------------------------------------------------------------------------
+// result emission: GroupByExpression::nextBatch (groupby.cc:187-220)
+// ---------------------------------------------------------------------------
+// EVQL_FLOAT_SUM_EXACT: (sum of high parts) * 2^31 + (sum of low parts) multiples of
+// 2^e, rounded to nearest once
+static double exact_sum_value(uint64_t hi, uint64_t lo, int e) {
+  const __int128 total = (__int128(int64_t(hi)) << 31) + __int128(int64_t(lo));
+  return std::ldexp(double(total), e);  // (int128 -> double rounds to nearest even)
+}
+
+static Value agg_value(const evql_query* q, const AggPlan& a, const uint64_t* st) {
+  Value v;
+  v.tag = 0;
+  const uint64_t w0 = st[a.first_word];
+  switch (a.fn) {
+    case EVQL_AGG_COUNT:
+    case EVQL_AGG_SUM_UINT64:
+    case EVQL_AGG_COUNT_DISTINCT_UINT64:
+      v.type = EVQL_T_UINT64;
+      v.bits = w0;
+      break;
+    case EVQL_AGG_SUM_INT64:
+      v.type = EVQL_T_INT64;
+      v.bits = w0;
+      break;
+    case EVQL_AGG_SUM_FLOAT64:
+      v.type = EVQL_T_FLOAT64;
+      v.bits = w0;
+      if (a.exact_index >= 0) {
+        const double d = exact_sum_value(w0, st[a.first_word + 1], q->fsum_exp[a.exact_index]);
+        memcpy(&v.bits, &d, 8);
+      }
+      break;
+    case EVQL_AGG_MIN_UINT64:
+    case EVQL_AGG_MAX_UINT64:
+    case EVQL_AGG_MIN_INT64:
+    case EVQL_AGG_MAX_INT64:
+    case EVQL_AGG_MIN_FLOAT64:
+    case EVQL_AGG_MAX_FLOAT64: {
+      v.type = (a.fn <= EVQL_AGG_MAX_UINT64) ? EVQL_T_UINT64
+               : (a.fn <= EVQL_AGG_MAX_INT64 ? EVQL_T_INT64 : EVQL_T_FLOAT64);
+      const uint64_t cnt = st[a.first_word + 1];
+      if (cnt == 0) {
+        v.bits = 0;
+        v.tag = EVQL_STAG_NULL;
+      } else {
+        v.bits = w0;
+      }
+      break;
+    }
+    default: {  // mean
+      v.type = EVQL_T_FLOAT64;
+      const uint64_t cnt = st[a.first_word + 1];
+      if (cnt == 0) {
+        v.bits = 0;
+        v.tag = EVQL_STAG_NULL;
+      } else {
+        double sum, m;
+        memcpy(&sum, &w0, 8);
+        m = sum / double(cnt);
+        memcpy(&v.bits, &m, 8);
+      }
+    }
+  }
+  (void) q;
+  return v;
+}
+
+static void put_varuint(std::vector<uint8_t>* b, uint64_t v) {
+  do {
+    uint8_t x = v & 0x7f;
+    v >>= 7;
+    if (v) x |= 0x80;
+    b->push_back(x);
+  } while (v);
+}
+
+// instance_savestate of each aggregate: count / sum = LEB128 varuint
+// (aggregate.cc:55-57,171-173,207-209); build-supplied: sum_float64 = 8 raw
+// bytes, min/max/mean = varuint(non-null count) + 8 raw bytes
+static void save_state(const evql_query* q, const AggPlan& a, const uint64_t* st,
+                       std::vector<uint8_t>* out, const uint64_t* rec = nullptr) {
+  const uint64_t w0 = st[a.first_word];
+  if (a.fn == EVQL_AGG_COUNT_DISTINCT_UINT64) {
+    // varuint size, then the values ascending (std::set order, aggregate.cc:111-117)
+    static const std::vector<uint64_t> none;
+    const std::vector<uint64_t>* vals = &none;
+    if (rec && a.distinct_index >= 0 && size_t(a.distinct_index) < q->distinct_values.size()) {
+      const uint64_t kind = rec[0];
+      const uint64_t ident = kind == 1 ? ~0ull : (kind == 2 ? 0 : rec[1]);
+      const uint64_t second = q->kp.key_mode == KEY_HASHED ? rec[2] : (kind == 2 ? 1 : 0);
+      const auto& sets = q->distinct_values[a.distinct_index];
+      auto hit = sets.find({q->kp.key_mode == KEY_NONE ? 0 : ident, second});
+      if (hit != sets.end()) vals = &hit->second;
+    }
+    put_varuint(out, vals->size());
+    for (uint64_t v : *vals) put_varuint(out, v);
+    return;
+  }
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(&w0);
+  switch (a.fn) {
+    case EVQL_AGG_COUNT:
+    case EVQL_AGG_SUM_UINT64:
+    case EVQL_AGG_SUM_INT64:
+      put_varuint(out, w0);
+      return;
+    case EVQL_AGG_SUM_FLOAT64:
+      if (a.exact_index >= 0) {  // the wire carries the rounded double
+        const double d = exact_sum_value(w0, st[a.first_word + 1], q->fsum_exp[a.exact_index]);
+        const uint8_t* pd = reinterpret_cast<const uint8_t*>(&d);
+        out->insert(out->end(), pd, pd + 8);
+        return;
+      }
+      out->insert(out->end(), p, p + 8);
+      return;
+    default: {
+      // min / max / mean.  A group without a non-NULL value: the state word still holds the
+      // operation's identity (min: all ones) -- on the wire an untouched state is 0
+      const uint64_t cnt = st[a.first_word + 1];
+      put_varuint(out, cnt);
+      static const uint8_t zero[8] = {0};
+      if (cnt == 0) {
+        out->insert(out->end(), zero, zero + 8);
+      } else {
+        out->insert(out->end(), p, p + 8);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ORDER BY .. LIMIT fused above the GROUP BY (orderby.cc:60-160, limit.cc:52-125)
+// ---------------------------------------------------------------------------
+Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,
+                       uint64_t offset) {
+  if (q->group_mode == EVQL_MODE_PARTIAL) {
+    return Status::error(EVQL_EARG, "ORDER BY / LIMIT above a partial aggregate");
+  }
+  if (n == 0 && limit < 0) {
+    return Status::error(EVQL_EARG, "can't execute ORDER BY: no sort specs");  // orderby.cc:53
+  }
+  std::vector<LoweredProgram> order(n);
+  std::vector<bool> desc(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    bool unsup = false;
+    std::string e = lower_program(specs[i].expr, &order[i], &unsup);
+    if (!e.empty()) return Status::error(unsup ? EVQL_ENOTSUP : EVQL_EARG, e);
+    if (order[i].is_aggregate) return Status::error(EVQL_EARG, "aggregate in ORDER BY");
+    std::vector<uint32_t> ins;
+    expr_inputs(order[i].call, &ins);
+    for (uint32_t in : ins) {
+      if (in >= q->select.size()) return Status::error(EVQL_EARG, "invalid input index");
+    }
+    switch (order[i].return_type) {  // there is no cmp#int64/bool;bool;
+      case EVQL_T_UINT64: case EVQL_T_INT64: case EVQL_T_FLOAT64: case EVQL_T_TIMESTAMP64:
+      case EVQL_T_STRING:
+        break;
+      default:
+        return Status::error(EVQL_EARG, "no comparator for the sort expression's type");
+    }
+    desc[i] = specs[i].descending != 0;
+  }
+  OrderKeyArgs ok{};
+  if (n > 0) {
+    const KernelPlan& kp = q->rplan();
+    const ExprPtr& e0 = order[0].call;
+    if (e0->kind != Expr::INPUT) {
+      return Status::error(EVQL_ENOTSUP, "first sort expression is not a plain output column");
+    }
+    const uint32_t si = e0->input;
+    const LoweredProgram& sp = q->select[si];
+    auto type_code = [](uint32_t t) { return t == EVQL_T_INT64 ? 1u : (t == EVQL_T_FLOAT64 ? 2u : 0u); };
+    ok.count_word = -1;
+    ok.descending = desc[0];
+    if (q->select_passthrough[si] && sp.return_type != EVQL_T_STRING) {
+      ok.from_ident = 1;
+      ok.word = 1;
+      ok.type = type_code(sp.return_type);
+    } else if (sp.is_aggregate && sp.call->kind == Expr::AGG_GET) {
+      const AggPlan& a = kp.aggs[q->select_agg_index[si]];
+      ok.word = uint32_t(1 + kp.state_word_base() + a.first_word);
+      switch (a.fn) {
+        case EVQL_AGG_COUNT:
+        case EVQL_AGG_COUNT_DISTINCT_UINT64:  // (one word: the number of distinct values)
+        case EVQL_AGG_SUM_UINT64: ok.type = 0; break;
+        case EVQL_AGG_SUM_INT64: ok.type = 1; break;
+        case EVQL_AGG_SUM_FLOAT64:
+          if (a.exact_index >= 0) {
+            return Status::error(EVQL_ENOTSUP, "ORDER BY an exact float sum is not fused");
+          }
+          ok.type = 2;
+          break;
+        case EVQL_AGG_MEAN_UINT64:
+        case EVQL_AGG_MEAN_INT64:
+        case EVQL_AGG_MEAN_FLOAT64:
+          ok.type = 2;
+          ok.is_mean = 1;
+          ok.count_word = int32_t(ok.word + 1);
+          break;
+        default:  // min / max
+          ok.type = type_code(sp.return_type);
+          ok.count_word = int32_t(ok.word + 1);
+      }
+    } else {
+      return Status::error(EVQL_ENOTSUP,
+                           "first sort expression cannot be read from a group record");
+    }
+  }
+  q->order.swap(order);
+  q->order_desc.swap(desc);
+  q->has_limit = limit >= 0;
+  q->limit = limit >= 0 ? uint64_t(limit) : 0;
+  q->offset = offset;
+  q->order_key = ok;
+  q->fetched = false;
+  return Status();
+}
+
+// cmp#int64/X;X; (boolean.cc:81-180): payloads only
+static int value_cmp(uint32_t type, const Value& a, const Value& b) {
+  switch (type) {
+    case EVQL_T_INT64: {
+      const int64_t l = int64_t(a.bits), r = int64_t(b.bits);
+      return l < r ? -1 : (l > r ? 1 : 0);
+    }
+    case EVQL_T_FLOAT64: {
+      double l, r;
+      memcpy(&l, &a.bits, 8);
+      memcpy(&r, &b.bits, 8);
+      return l < r ? -1 : (l > r ? 1 : 0);
+    }
+    case EVQL_T_STRING: {
+      const size_t m = std::min(a.str.size(), b.str.size());
+      const int c = m ? strncmp(a.str.data(), b.str.data(), m) : 0;
+      if (c != 0) return c < 0 ? -1 : 1;
+      return a.str.size() < b.str.size() ? -1 : (a.str.size() > b.str.size() ? 1 : 0);
+    }
+    default:
+      return a.bits < b.bits ? -1 : (a.bits > b.bits ? 1 : 0);
+  }
+}
+
+// The scan select list of fetched group g: the scan columns of the group's first row as
+// Values (`scan_vals`, scratch), then every scan select expression over them.  Plans without
+// a first row leave `sel_inputs` as it is; their select expressions read no inputs.
+static Status group_select_inputs(const evql_query* q, uint64_t g, std::vector<Value>* scan_vals,
+                                  std::vector<Value>* sel_inputs) {
+  const KernelPlan& kp = q->rplan();
+  const uint32_t nc = uint32_t(kp.cols.size());
+  scan_vals->resize(nc);
+  sel_inputs->resize(q->scan_select.size());
+  if (!kp.need_first_row) return Status();
+  for (uint32_t c = 0; c < nc; ++c) {
+    const ColAccess& ca = kp.cols[c];
+    Value v;
+    v.type = ca.stype;
+    v.tag = q->first_tags[uint64_t(c) * q->ngroups + g];
+    const uint64_t raw = q->first_vals[uint64_t(c) * q->ngroups + g];
+    if (ca.string_hash) {
+      if (!v.tag) {
+        const uint64_t off = q->first_str_off[uint64_t(c) * q->ngroups + g];
+        v.str.assign(reinterpret_cast<const char*>(q->first_str_heap.data()) + off,
+                     size_t(raw >> 40));
+        // A cell of the Dremel scan is a boxed SValue (CSTableScan.cc:300-330): a string
+        // of 11 bytes is exactly the 16 bytes of the inline buffer, whose last byte --
+        // the value's tag -- also holds STAG_INLINE (svalue.cc:346-368).  X_INPUT copies
+        // the bytes as they lie, so the tag 0x80 reaches the group key's SHA1
+        // (PartialGroupBy keys) and the output vectors.  Found by the round-3 soak.
+        if (q->nested && v.str.size() == 11) v.tag = 0x80;
+      }
+    } else if (ca.stype == EVQL_T_FLOAT64 && ca.from_uint_to_float) {
+      double d = double(raw);
+      memcpy(&v.bits, &d, 8);
+    } else if (ca.stype == EVQL_T_BOOL) {
+      v.bits = raw != 0;
+    } else {
+      v.bits = raw;
+    }
+    (*scan_vals)[c] = v;
+  }
+  for (size_t j = 0; j < q->scan_select.size(); ++j) {
+    std::string e = eval_expr(q->scan_select[j].call, *scan_vals, nullptr, &(*sel_inputs)[j]);
+    if (!e.empty()) return Status::error(EVQL_ERUNTIME, e);
+  }
+  return Status();
+}
+
+// value of select expression i of fetched record `rec` as EVQL_MODE_FINAL emits it: an
+// expression over the group's aggregate, the group key itself, or an expression over the
+// scan select list (`inputs`)
+static Status select_value(const evql_query* q, size_t i, const uint64_t* rec,
+                           const std::vector<Value>& inputs, Value* out) {
+  const KernelPlan& kp = q->rplan();
+  const LoweredProgram& lp = q->select[i];
+  std::string e;
+  if (lp.is_aggregate) {
+    Value av = agg_value(q, kp.aggs[q->select_agg_index[i]], rec + 1 + kp.state_word_base());
+    e = eval_expr(lp.call, inputs, &av, out);
+  } else if (q->select_passthrough[i]) {
+    const bool null_key = rec[0] == 2;
+    out->bits = null_key ? 0 : rec[1];
+    out->tag = null_key ? uint8_t(EVQL_STAG_NULL) : uint8_t(0);
+  } else {
+    e = eval_expr(lp.call, inputs, nullptr, out);
+  }
+  if (!e.empty()) return Status::error(EVQL_ERUNTIME, e);
+  out->type = lp.return_type;
+  return Status();
+}
+
+// the select-list values of fetched record g (EVQL_MODE_FINAL), as query_next_batch emits
+// them; ORDER BY evaluates its sort expressions over these
+static Status final_row_values(evql_query* q, uint64_t g, std::vector<Value>* outs) {
+  std::vector<Value> scan_vals, sel_inputs;
+  Status st = group_select_inputs(q, g, &scan_vals, &sel_inputs);
+  if (!st.ok()) return st;
+  const std::vector<Value> none;
+  const std::vector<Value>& inputs = q->rplan().need_first_row ? sel_inputs : none;
+  outs->assign(q->select.size(), Value());
+  for (size_t i = 0; i < outs->size(); ++i) {
+    st = select_value(q, i, &q->records[g * q->rec_stride], inputs, &(*outs)[i]);
+    if (!st.ok()) return st;
+  }
+  return Status();
+}
+
+// orders the fetched records by every sort spec and applies OFFSET / LIMIT
+static Status order_fetched(evql_query* q) {
+  const uint64_t n = q->ngroups;
+  q->emit_order.clear();
+  if (q->order.empty() && !q->has_limit) return Status();
+  std::vector<uint64_t> idx(n);
+  for (uint64_t i = 0; i < n; ++i) idx[i] = i;
+  if (!q->order.empty()) {
+    const size_t ns = q->order.size();
+    std::vector<Value> keys(n * ns), row;
+    for (uint64_t g = 0; g < n; ++g) {
+      Status st = final_row_values(q, g, &row);
+      if (!st.ok()) return st;
+      for (size_t j = 0; j < ns; ++j) {
+        std::string e = eval_expr(q->order[j].call, row, nullptr, &keys[g * ns + j]);
+        if (!e.empty()) return Status::error(EVQL_ERUNTIME, e);
+      }
+    }
+    std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+      for (size_t j = 0; j < ns; ++j) {
+        const int c = value_cmp(q->order[j].return_type, keys[a * ns + j], keys[b * ns + j]);
+        if (c != 0) return q->order_desc[j] ? c > 0 : c < 0;
+      }
+      return false;
+    });
+  }
+  uint64_t lo = 0, hi = n;
+  if (q->has_limit) {
+    lo = std::min(q->offset, n);
+    hi = q->limit == 0 ? lo : std::min(n, q->offset + q->limit);
+  }
+  q->emit_order.assign(idx.begin() + lo, idx.begin() + hi);
+  return Status();
+}
+
+Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows) {
+  if (!q->executed) return Status::error(EVQL_EARG, "execute() was not called");
+  if (!q->fetched) {
+    Status st = fetch_results(q);
+    if (!st.ok()) return st;
+    st = order_fetched(q);
+    if (!st.ok()) return st;
+  }
+  if (q->demit.active) {
+    // slices of the columns packed on the device (emit_on_device)
+    const evql_query::DeviceEmit& de = q->demit;
+    const uint64_t left = q->ngroups - q->emit_pos;
+    const uint64_t m = std::min<uint64_t>(left, max_rows);
+    for (size_t i = 0; i < de.col.size(); ++i) {
+      if (de.elem[i]) {
+        cols[i].data = de.col[i] + q->emit_pos * de.elem[i];
+        cols[i].size = size_t(m) * de.elem[i];
+      } else {
+        const uint64_t b0 = de.off[i][q->emit_pos], b1 = de.off[i][q->emit_pos + m];
+        cols[i].data = de.col[i] + b0;
+        cols[i].size = size_t(b1 - b0);
+      }
+    }
+    q->emit_pos += m;
+    *nrows = size_t(m);
+    return Status();
+  }
+  const KernelPlan& kp = q->rplan();
+  const size_t nsel = q->select.size();
+  const bool partial = q->group_mode == EVQL_MODE_PARTIAL;
+  q->out_cols.assign(partial ? 2 : nsel, std::vector<uint8_t>());
+  const size_t rw = q->rec_stride;
+  size_t emitted = 0;
+  std::vector<Value> scan_vals, sel_inputs;
+  const std::vector<Value> none;
+  const bool reordered = !q->order.empty() || q->has_limit;
+  const uint64_t emit_total = reordered ? q->emit_order.size() : q->ngroups;
+  while (q->emit_pos < emit_total && emitted < max_rows) {
+    const uint64_t g = reordered ? q->emit_order[q->emit_pos] : q->emit_pos;
+    const uint64_t* rec = &q->records[g * rw];
+    const uint64_t kind = rec[0], ident = rec[1];
+    const uint64_t* st = rec + 1 + kp.state_word_base();
+    Status sti = group_select_inputs(q, g, &scan_vals, &sel_inputs);
+    if (!sti.ok()) return sti;
+    const std::vector<Value>& inputs = kp.need_first_row ? sel_inputs : none;
+    std::vector<uint8_t> pdata;  // PARTIAL mode: concatenated saved states
+    for (size_t i = 0; i < nsel; ++i) {
+      const LoweredProgram& lp = q->select[i];
+      Value out;
+      if (partial && lp.is_aggregate) {
+        save_state(q, kp.aggs[q->select_agg_index[i]], st, &pdata, rec);
+        continue;
+      }
+      Status stv = select_value(q, i, rec, inputs, &out);
+      if (!stv.ok()) return stv;
+      if (partial) {
+        // SValue::encode (svalue.cc): u8 type, lenenc(value || tag bytes)
+        std::vector<uint8_t> enc;
+        append_svector(lp.return_type, out, &enc);
+        // A reference quirk kept for byte-identical wire rows: the value is boxed in an
+        // SValue whose 16-byte inline buffer ends in its tag byte, where setData also keeps
+        // the internal STAG_INLINE flag (svalue.cc:346-368).  A value of exactly 16 bytes --
+        // a string of 11 -- therefore leaves with bit 7 set in its tag.
+        if (enc.size() == 16) enc.back() |= 0x80;
+        pdata.push_back(uint8_t(lp.return_type));
+        put_varuint(&pdata, enc.size());
+        pdata.insert(pdata.end(), enc.begin(), enc.end());
+      } else {
+        append_svector(lp.return_type, out, &q->out_cols[i]);
+      }
+    }
+    if (partial) {
+      // group key = SHA1 of the tuple bytes, LAST group expression first
+      // (groupby.cc:112-135: the VM stack grows downward)
+      std::vector<uint8_t> tuple;
+      for (size_t gi = q->group.size(); gi-- > 0;) {
+        Value gv;
+        if (kp.key_mode == KEY_EXACT) {
+          gv.type = q->group[gi].return_type;
+          gv.bits = kind == 2 ? 0 : ident;
+          gv.tag = kind == 2 ? EVQL_STAG_NULL : 0;
+        } else {
+          std::string e = eval_expr(q->group[gi].call, sel_inputs, nullptr, &gv);
+          if (!e.empty()) return Status::error(EVQL_ERUNTIME, e);
+        }
+        append_svector(q->group[gi].return_type, gv, &tuple);
+      }
+      Sha1Digest d = sha1(tuple.data(), tuple.size());
+      Value kv, dv;
+      kv.str.assign(reinterpret_cast<const char*>(d.bytes), 20);
+      dv.str.assign(reinterpret_cast<const char*>(pdata.data()), pdata.size());
+      append_svector(EVQL_T_STRING, kv, &q->out_cols[0]);
+      append_svector(EVQL_T_STRING, dv, &q->out_cols[1]);
+    }
+    ++q->emit_pos;
+    ++emitted;
+  }
+  for (size_t i = 0; i < q->out_cols.size(); ++i) {
+    cols[i].data = q->out_cols[i].data();
+    cols[i].size = q->out_cols[i].size();
+  }
+  *nrows = emitted;
+  return Status();
+}
+
+}  // namespace evql

@@ -91,14 +91,22 @@ struct evql_ctx {
 };
 
 namespace evql {
-// owning device pointer for temporaries: freed on every exit path (HIP_TRY returns
-// early on errors)
+// owning device pointer (move-only): freed on every exit path (HIP_TRY returns early on
+// errors), or with the cache entry that holds it
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.release();
+    }
+    return *this;
+  }
   ~DevBuf() { reset(); }
   hipError_t alloc(size_t bytes) {
     reset();
@@ -195,23 +203,24 @@ struct evql_table {
   // deepest repeated column is `leaf` -- key (column, leaf) layout indices.  Like
   // `materialized`, decoded once per table and shared by every operator.
   struct NestedFlat {
-    uint64_t* d_values = nullptr;  // per row: value bits; strings: (len << 40 | position)
+    evql::DevBuf<uint64_t> d_values;  // per row: value bits; strings: (len << 40 | position)
     uint64_t nflat = 0;
-    uint64_t* d_hash = nullptr;    // strings: 64-bit hash of the row's bytes
+    evql::DevBuf<uint64_t> d_hash;    // strings: 64-bit hash of the row's bytes
     // the values once more as bit-packed pages of 8 / 16 / 32 bits (when their maximum
     // fits): what the fused kernel streams instead of the 8-byte words
-    uint8_t* d_packed = nullptr;
-    uint64_t* d_packed_pages = nullptr;
+    evql::DevBuf<uint8_t> d_packed;
+    evql::DevBuf<uint64_t> d_packed_pages;
     uint32_t packed_bits = 0;
     bool pack_tried = false;
   };
   std::map<std::pair<int, int>, NestedFlat> nested_cache;
   // record scans (WITHIN RECORD): the leaf's decoded repetition levels (one byte
   // per slot) and the scanned per-tile counts of its level-0 slots (= records
-  // started before the tile), keyed by the leaf's layout index
+  // started before the tile), keyed by the leaf's layout index.  An entry outlives
+  // every query on the table: operators hold pointers to it.
   struct LeafLevels {
-    uint8_t* levels = nullptr;
-    uint64_t* rec_offsets = nullptr;
+    evql::DevBuf<uint8_t> levels;
+    evql::DevBuf<uint64_t> rec_offsets;
   };
   std::map<int, LeafLevels> leaf_cache;
   ~evql_table();
@@ -251,7 +260,7 @@ struct evql_query {
   uint8_t* d_row_filter = nullptr;
   bool row_filter_owned = true;  // false: the bits belong to an evql_lsm_chain
   // nested scans: one bit per record on entry; query_prepare replaces it by its expansion to
-  // one bit per flattened row where the two differ (runtime.cc expand_record_filter)
+  // one bit per flattened row where the two differ (nested.cc expand_record_filter)
   uint64_t reported_rows_scanned = ~0ull;  // != ~0: the reference's count, where it is not the row range
   // evql_query_create_chain: this query scans the first table of a partition's chain;
   // `chain` holds the queries of the tables behind it (owned).  After execute their
@@ -354,7 +363,7 @@ struct evql_query {
   std::vector<uint64_t> first_str_off;  // [col][group] offset into the heap
   uint64_t emit_pos = 0;
   std::vector<std::vector<uint8_t>> out_cols;
-  // large results packed on the device (runtime.cc emit_on_device): every output column
+  // large results packed on the device (results.cc emit_on_device): every output column
   // of ALL groups as SVector bytes in pinned host memory, next_batch hands out slices
   struct DeviceEmit {
     bool active = false;
@@ -383,10 +392,22 @@ struct evql_writer {
   std::vector<evql::ColumnSpec> specs;
 };
 
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      return Status::error(EVQL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    }                                                                                        \
+  } while (0)
+
 namespace evql {
+// capi.cc: the calling thread's last error
 void set_last_error(const std::string& m);
 int fail(int code, const std::string& m);
 
+// kernel_cache.cc
+void set_cache_dir(const std::string& d);
+Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache);
 Status compile_kernel(evql_ctx* ctx, const std::string& source, Module* out,
                       bool load_module);
 Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan,
@@ -398,6 +419,63 @@ Status table_rt_column(evql_table* t, const std::string& name, RtColumn* out,
 Status upload_page_tables(evql_table* t);
 // string_dict.cc: the (cached) dictionary of STRING column `li`; built on first use
 Status table_string_dict(evql_table* t, int li, StringDict** out);
+
+// table.cc
+Status table_from_image(evql_ctx* ctx, const void* image, size_t len, bool keep_host,
+                        evql_table** out);
+inline uint64_t padded_rows(uint64_t n) {
+  const uint64_t pad = 8192;  // largest tile
+  return (n + pad - 1) / pad * pad + pad;
+}
+// bit width of a bit-packed stream: bitpack_width of the 4-byte header of its first page
+Status stream_bits(evql_table* t, const std::vector<PageRef>& pages, uint32_t* bits);
+// Where the `nvalues` defined values of column `li` are read from: its data pages as they lie
+// (PLAIN64 / PLAIN32 / BITPACKED with its width), or SOA over a buffer decoded (LEB128) or
+// located (STRING_PLAIN: (len << 40) | position) here.  That buffer is `dst` when the caller
+// has one for LEB128 values, else it is allocated into `*owned`.
+Status defined_value_source(evql_table* t, int li, uint64_t nvalues, uint64_t* dst, RtColumn* src,
+                            DevBuf<uint64_t>* owned);
+Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<uint8_t>* d_packed,
+                   DevBuf<uint64_t>* d_packed_pages, uint32_t* bits_out);
+Status materialize_column(evql_table* t, const ColAccess& ca);
+
+// nested.cc: the scans of a nested query, run by query_prepare
+using LeafLevels = evql_table::LeafLevels;
+Status materialize_nested(evql_query* q, const std::vector<ColAccess>& cols,
+                          std::vector<uint64_t*>* flat_out, uint64_t* nrows_out,
+                          const LeafLevels** keep, std::vector<uint64_t*>* strpos_out = nullptr);
+Status materialize_nested_zip(evql_query* q, const std::vector<ColAccess>& cols,
+                              std::vector<uint64_t*>* flat_out, uint64_t* nrows_out,
+                              std::vector<uint64_t*>* strpos_out);
+Status materialize_within_record(evql_query* q);
+Status expand_record_filter(evql_query* q, const LeafLevels* leaf);
+Status apply_where_resets(evql_query* q, const LeafLevels* leaf);
+
+// value_bounds.cc
+Status choose_exact_sum_scales(evql_query* q);
+Status choose_tuple_widths(evql_query* q);
+
+// query_run.cc
+Status query_prepare(evql_query* q);
+Status query_launch(evql_query* q);
+Status query_finish(evql_query* q);
+Status query_reset(evql_query* q);
+Status query_recount(evql_query* q);
+Status query_dense_into_table(evql_query* q);
+Status query_reserve_groups(evql_query* q, uint64_t extra);
+Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, uint64_t n);
+void fill_host_args(evql_query* q, HostArgs* ap);
+
+// results.cc
+Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,
+                       uint64_t offset);
+Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
+
+// exchange.cc / lsm.cc
+Status chain_merge(evql_query* head);
+size_t lsm_chain_parts(const evql_lsm_chain* ch, std::vector<evql_table*>* tables,
+                       std::vector<const uint8_t*>* d_filters);
+evql_ctx* lsm_chain_ctx(const evql_lsm_chain* ch);
 // the query's groups as dense records of rplan()'s layout: `dense` holds the first `nd`
 // groups, the remaining ngroups - nd sit in the HBM group table (compact them from there)
 struct RecordsView {

@@ -22,18 +22,6 @@
 
 namespace evql {
 
-Status query_prepare(evql_query* q);
-Status query_launch(evql_query* q);
-Status query_finish(evql_query* q);
-
-#define DICT_HIP(expr)                                                                       \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      return Status::error(EVQL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    }                                                                                        \
-  } while (0)
-
 static Status build_dict(evql_table* t, int li, StringDict* d) {
   evql_ctx* ctx = t->ctx;
   hipStream_t s = ctx->stream;
@@ -81,15 +69,15 @@ static Status build_dict(evql_table* t, int li, StringDict* d) {
   }
   const uint32_t W = uint32_t(kp.words_per_slot());  // identity, first row, count
   DevBuf<uint64_t> d_rec;
-  DICT_HIP(d_rec.alloc(D * (W + 1) * 8));
+  HIP_TRY(d_rec.alloc(D * (W + 1) * 8));
   {
     const uint64_t nd = std::min(dq->dense_n, D);
-    if (nd) DICT_HIP(hipMemcpyAsync(d_rec, dq->d_dense, nd * (W + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (nd) HIP_TRY(hipMemcpyAsync(d_rec, dq->d_dense, nd * (W + 1) * 8, hipMemcpyDeviceToDevice, s));
     if (D > nd) {
       uint64_t* d_cnt = dq->d_counters + 6;
-      DICT_HIP(hipMemsetAsync(d_cnt, 0, 8, s));
-      DICT_HIP(launch_table_compact(dq->d_gtab, dq->gcap, dq->gcap + 8, W, d_rec.p + nd * (W + 1),
-                                    D - nd, d_cnt, s));
+      HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+      HIP_TRY(launch_table_compact(dq->d_gtab, dq->gcap, dq->gcap + 8, W, d_rec.p + nd * (W + 1),
+                                   D - nd, d_cnt, s));
     }
   }
   // ---- 2. hash -> code -------------------------------------------------------------------------
@@ -98,25 +86,25 @@ static Status build_dict(evql_table* t, int li, StringDict* d) {
   while (cap < 2 * D) cap <<= 1;
   DevBuf<uint64_t> d_tab, d_special;
   DevBuf<uint32_t> d_status;
-  DICT_HIP(d_tab.alloc(cap * 2 * 8));
-  DICT_HIP(d_special.alloc(16));
-  DICT_HIP(d_status.alloc(16));
-  DICT_HIP(hipMemsetAsync(d_tab, 0xff, cap * 2 * 8, s));
-  DICT_HIP(hipMemsetAsync(d_special, 0xff, 16, s));
-  DICT_HIP(hipMemsetAsync(d_status, 0, 16, s));
-  DICT_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_entries), D * 3 * 8));
+  HIP_TRY(d_tab.alloc(cap * 2 * 8));
+  HIP_TRY(d_special.alloc(16));
+  HIP_TRY(d_status.alloc(16));
+  HIP_TRY(hipMemsetAsync(d_tab, 0xff, cap * 2 * 8, s));
+  HIP_TRY(hipMemsetAsync(d_special, 0xff, 16, s));
+  HIP_TRY(hipMemsetAsync(d_status, 0, 16, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_entries), D * 3 * 8));
   // codes: 4 bytes per row, laid out as 512 KiB "pages" of 131,072 values (the PLAIN32
   // accessor of the fused kernel), zero slack for the tile overhang
   const uint64_t per_page = 131072;
   const uint64_t npages = (n + per_page - 1) / per_page;
   const uint64_t bytes = npages * per_page * 4 + (1 << 20);
-  DICT_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_codes), bytes));
-  DICT_HIP(hipMemsetAsync(d->d_codes, 0, bytes, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_codes), bytes));
+  HIP_TRY(hipMemsetAsync(d->d_codes, 0, bytes, s));
   std::vector<uint64_t> offs;
   for (uint64_t p = 0; p < npages; ++p) offs.push_back(p * per_page * 4);
   offs.push_back(offs.back());
-  DICT_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_code_pages), offs.size() * 8));
-  DICT_HIP(hipMemcpyAsync(d->d_code_pages, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_code_pages), offs.size() * 8));
+  HIP_TRY(hipMemcpyAsync(d->d_code_pages, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
   DictArgs da{};
   da.records = d_rec;
   da.ncodes = D;
@@ -132,12 +120,12 @@ static Status build_dict(evql_table* t, int li, StringDict* d) {
   da.nrows = n;
   da.codes = d->d_codes;
   da.status = d_status;
-  DICT_HIP(launch_dict_insert(da, s));
+  HIP_TRY(launch_dict_insert(da, s));
   // ---- 3. codes + the proof of exactness --------------------------------------------------------
-  DICT_HIP(launch_dict_assign(da, s));
+  HIP_TRY(launch_dict_assign(da, s));
   uint32_t status[4] = {0, 0, 0, 0};
-  DICT_HIP(hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, s));
-  DICT_HIP(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(status, d_status, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   if (status[0] != 0) {
     d->why = status[0] & 2u ? "two different strings share a 64-bit hash"
                             : "a row's hash is missing from the dictionary";

@@ -152,7 +152,7 @@ def test_partitioned_high_cardinality_path(mixed):
 
 def test_partition_tuple_widths(mixed):
     """tuple members that the table's column maxima bound below 2^32 travel as 4 bytes
-    through scatter / refine / aggregate (runtime.cc choose_tuple_widths): the layouts
+    through scatter / refine / aggregate (value_bounds.cc choose_tuple_widths): the layouts
     the generator picks, and every narrow member kind against the oracle"""
     import re
     t, img, c = mixed
