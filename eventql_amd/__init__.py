@@ -385,8 +385,14 @@ class Query:
         _check(lib().evql_query_set_order(self.h, order.specs, order.n, order.limit,
                                           order.offset))
 
-    def execute(self):
-        _check(lib().evql_query_execute(self.h, None, None))
+    def execute(self, heartbeat=None):
+        """heartbeat: callable() -> int (non-zero asks to stop), evql_heartbeat_fn"""
+        if heartbeat is None:
+            _check(lib().evql_query_execute(self.h, None, None))
+            return
+        # (a bare scan keeps beating it from next_batch: it lives as long as the query)
+        self._heartbeat = K.HEARTBEAT_FN(lambda user: int(heartbeat()))
+        _check(lib().evql_query_execute(self.h, C.cast(self._heartbeat, C.c_void_p), None))
 
     def launch(self):
         _check(lib().evql_query_launch(self.h))

@@ -621,8 +621,10 @@ csql::TableExpression* GpuLowering::lowerScan(csql::Transaction* txn,
 }
 
 /* ORDER BY / LIMIT directly above a lowered GROUP BY: into the operator (its top-k runs
- * on the device over the dense group records); anything else: the reference's operators
- * stacked on the input that was just built (scheduler.cc:36-49, 95-132) */
+ * on the device over the dense group records); a LIMIT directly above a lowered bare scan
+ * too (its rows are ordered: tiles outside the range are never emitted), an ORDER BY above
+ * one is refused by the library; anything else: the reference's operators stacked on the
+ * input that was just built (scheduler.cc:36-49, 95-132) */
 ScopedPtr<csql::TableExpression> GpuLowering::orderBy(csql::Transaction* txn,
                                                       csql::ExecutionContext* execution_context,
                                                       csql::OrderByNode* node,

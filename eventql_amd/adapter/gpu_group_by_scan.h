@@ -213,7 +213,8 @@ struct GpuSchedulerOptions {
   GpuSchedulerOptions() : lower_group_by(true), lower_scans(false), partial(false),
                           strict(false), fuse_order_by(true) {}
   bool lower_group_by; /* GroupByExpression + scan -> one fused operator */
-  bool fuse_order_by;  /* ORDER BY / LIMIT directly above it -> into the operator */
+  bool fuse_order_by;  /* ORDER BY / LIMIT directly above it (LIMIT: above a lowered scan
+                          too) -> into the operator */
   bool lower_scans;    /* bare FastCSTableScan / CSTableScan -> GPU scan operator */
   bool partial;        /* build PartialGroupByExpression's twin (a data node) */
   bool strict;         /* tests: RAISE instead of falling back to the CPU operators */
@@ -303,7 +304,7 @@ protected:
   ScopedPtr<csql::TableExpression> buildOrderByExpression(
       csql::Transaction* txn, csql::ExecutionContext* execution_context,
       RefPtr<csql::OrderByNode> node) override {
-    if (!gpu_.opts_.lower_group_by || !gpu_.opts_.fuse_order_by) {
+    if (!(gpu_.opts_.lower_group_by || gpu_.opts_.lower_scans) || !gpu_.opts_.fuse_order_by) {
       return Base::buildOrderByExpression(txn, execution_context, node);
     }
     return gpu_.orderBy(txn, execution_context, node.get(),
@@ -315,7 +316,7 @@ protected:
   ScopedPtr<csql::TableExpression> buildLimit(
       csql::Transaction* txn, csql::ExecutionContext* execution_context,
       RefPtr<csql::LimitNode> node) override {
-    if (!gpu_.opts_.lower_group_by || !gpu_.opts_.fuse_order_by) {
+    if (!(gpu_.opts_.lower_group_by || gpu_.opts_.lower_scans) || !gpu_.opts_.fuse_order_by) {
       return Base::buildLimit(txn, execution_context, node);
     }
     return gpu_.limit(execution_context, node.get(),

@@ -805,6 +805,49 @@ __global__ void __launch_bounds__(1024) k_exclusive_scan(u64* data, u64 n, u64* 
   if (threadIdx.x == 0 && total) *total = carry_s;
 }
 
+// per-tile counts (u32) -> offsets (u64): out[i] = sum of counts[0 .. i), out[n] = the total.
+// One workgroup, four consecutive counts per thread and step (1e9 rows are 1.2e5 tiles:
+// 30 steps).
+__global__ void __launch_bounds__(1024) k_scan_u32(const u32* counts, u64 n, u64* out) {
+  __shared__ u64 wsum[16];
+  __shared__ u64 carry_s;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (u64 base = 0; base < n; base += 4096) {
+    const u64 i = base + (u64) threadIdx.x * 4;
+    u64 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? (u64) counts[i + j] : 0;
+    const u64 mine = v[0] + v[1] + v[2] + v[3];
+    u64 incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      u32 lo = (u32) incl, hi = (u32) (incl >> 32);
+      lo = __shfl_up(lo, d, 64);
+      hi = __shfl_up(hi, d, 64);
+      if ((int) (threadIdx.x & 63) >= d) incl += (u64) lo | ((u64) hi << 32);
+    }
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    u64 off = carry_s, tot = 0;
+    for (u32 w = 0; w < 16; ++w) {
+      if (w < wave) off += wsum[w];
+      tot += wsum[w];
+    }
+    u64 run = off + incl - mine;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (i + j < n) out[i + j] = run;
+      run += v[j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) carry_s += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[n] = carry_s;
+}
+
 __global__ void __launch_bounds__(kBlock) k_expand_nullable(const u8* image, RtColumn src,
                                                             const u8* tags,
                                                             const u64* tile_offsets, u64 nrows,
@@ -2152,6 +2195,11 @@ hipError_t launch_dlevel_tags(const uint8_t* image, const uint64_t* dlevel_pages
   hipLaunchKernelGGL(k_dlevel_tags, dim3((unsigned) ntiles), dim3(kBlock), 0, s, image,
                      (const u64*) dlevel_pages, dbits, dmax, (u64) nrows, tags,
                      (u64*) tile_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_scan_u32(const uint32_t* counts, uint64_t n, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, (const u32*) counts, (u64) n, (u64*) out);
   return hipGetLastError();
 }
 

@@ -679,6 +679,10 @@ int evql_query_execute(evql_query_t* q, evql_heartbeat_fn hb, void* user) {
   if (!st.ok()) return ret(st);
   for (evql_query* p : hbs.qs) aborted = aborted || p->hb_abort;
   if (aborted || (hb && hb(user) != 0)) return fail(EVQL_ERUNTIME, "query aborted by heartbeat");
+  if (q->kp.bare_scan) {  // (its windows are emitted by next_batch)
+    q->bare.hb = hb;
+    q->bare.hb_user = user;
+  }
   return EVQL_OK;
   API_CATCH
 }
@@ -686,10 +690,14 @@ int evql_query_execute(evql_query_t* q, evql_heartbeat_fn hb, void* user) {
 int evql_query_column_count(const evql_query_t* q) {
   // PartialGroupByExpression emits (key, data) string pairs (groupby.cc:484-491)
   if (q->group_mode == EVQL_MODE_PARTIAL) return 2;
+  if (q->kp.bare_scan) return int(q->scan_select.size());  // the scan select list itself
   return int(q->select.size());
 }
 int evql_query_column_type(const evql_query_t* q, int idx) {
   if (q->group_mode == EVQL_MODE_PARTIAL) return idx >= 0 && idx < 2 ? EVQL_T_STRING : -1;
+  if (q->kp.bare_scan) {
+    return idx >= 0 && size_t(idx) < q->scan_select.size() ? int(q->scan_select[idx].return_type) : -1;
+  }
   if (idx < 0 || size_t(idx) >= q->select.size()) return -1;
   return int(q->select[idx].return_type);
 }
@@ -731,6 +739,7 @@ uint32_t evql_query_record_words(const evql_query_t* q) {
 
 int evql_query_partial_view(evql_query_t* q, evql_partial_view_t* out) {
   if (!q || !out) return fail(EVQL_EARG, "null argument");
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   if (q->merged) return fail(EVQL_EARG, "the query's groups were merged (exchange / chain): emit them with next_batch");
   if (q->dict_key) return fail(EVQL_ENOTSUP, "plan groups by dictionary codes: merge it with evql_query_exchange");
   {
@@ -747,6 +756,7 @@ int evql_query_partial_view(evql_query_t* q, evql_partial_view_t* out) {
 int evql_query_export_groups(evql_query_t* q, void* device_dst, uint64_t max_groups,
                              uint64_t* n_groups) {
   API_TRY
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   if (q->merged) return fail(EVQL_EARG, "the query's groups were merged (exchange / chain): emit them with next_batch");
   if (q->kp.n_exact > 0 && !(q->float_sum_bound > 0)) {
     // the records carry integer multiples of a quantum derived from ONE table's maxima;
@@ -786,6 +796,7 @@ int evql_query_export_groups(evql_query_t* q, void* device_dst, uint64_t max_gro
 
 int evql_query_import_groups(evql_query_t* q, const void* device_src, uint64_t n_groups) {
   API_TRY
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   if (q->merged) return fail(EVQL_EARG, "the query's groups were merged (exchange / chain): emit them with next_batch");
   if (q->kp.n_exact > 0 && !(q->float_sum_bound > 0)) {
     // the records carry integer multiples of a quantum derived from ONE table's maxima;
@@ -842,6 +853,7 @@ int evql_query_export_pairs(evql_query_t* q, uint32_t which, void* device_dst, u
                             uint64_t* n_pairs) {
   API_TRY
   if (!q || !n_pairs) return fail(EVQL_EARG, "null argument");
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   if (which >= uint32_t(q->kp.n_distinct)) return fail(EVQL_EARG, "no such count_distinct aggregate");
   if (q->merged) return fail(EVQL_EARG, "the query's groups were merged (exchange / chain): emit them with next_batch");
   hipStream_t s = q->ctx->stream;
@@ -865,6 +877,7 @@ int evql_query_import_pairs(evql_query_t* q, uint32_t which, const void* device_
                             uint64_t n_pairs) {
   API_TRY
   if (!q || (!device_src && n_pairs)) return fail(EVQL_EARG, "null argument");
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   if (which >= uint32_t(q->kp.n_distinct)) return fail(EVQL_EARG, "no such count_distinct aggregate");
   if (q->merged) return fail(EVQL_EARG, "the query's groups were merged (exchange / chain): emit them with next_batch");
   if (!q->d_gtab) return fail(EVQL_EARG, "import the group records first");

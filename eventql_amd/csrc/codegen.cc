@@ -54,6 +54,8 @@ struct Emitter {
 
   // string literals referenced by compares; declared at file scope by the caller
   std::vector<std::string> string_literals;
+  // index of this emitter's first literal among the translation unit's `evql_slit<i>`
+  size_t lit_base = 0;
 
   std::string str_operand(const ExprPtr& x) {
     char b[96];
@@ -61,7 +63,7 @@ struct Emitter {
       snprintf(b, sizeof(b), "evql_col_str(A, A.col[%u], row)", x->input);
       return b;
     }
-    snprintf(b, sizeof(b), "evql_lit_str(evql_slit%zu, %zuu)", string_literals.size(),
+    snprintf(b, sizeof(b), "evql_lit_str(evql_slit%zu, %zuu)", lit_base + string_literals.size(),
              x->lit_str.size());
     string_literals.push_back(x->lit_str);
     return b;

@@ -99,6 +99,12 @@ struct KernelPlan {
   // kernel (evql_where_rows) writes the predicate of every row, from which the runtime
   // reproduces the reference's reset of parent values behind a rejected row
   bool where_rows_kernel = false;
+  // bare scan (neither GROUP BY nor aggregates): the values of `scan_out` -- the scan
+  // select list over scan columns -- leave the device for every passing row, in row order
+  // (codegen_kernels.inc bare_scan_kernels: evql_scan_count / evql_scan_emit)
+  bool bare_scan = false;
+  std::vector<ExprPtr> scan_out;
+  std::vector<bool> scan_out_nullable;  // may the value carry STAG_NULL?
   int tile_rows() const { return block * 2 * unroll; }
 };
 

@@ -4,6 +4,8 @@
 // group identity, aggregate arguments); three kernel skeletons consume it:
 //
 //   evql_scan_agg        fused scan -> filter -> GROUP BY (LDS table -> HBM table)
+//   evql_scan_count /    bare scans (no GROUP BY, no aggregate): the passing rows' select
+//   evql_scan_emit       values in row order, window by window
 //   evql_part_count /    high-cardinality plans: radix-partition the passing
 //   evql_part_scatter /  rows by 12 hash bits into 4096 buckets of (identity,
 //   evql_part_aggregate  update words) tuples with streaming traffic, then
@@ -159,34 +161,37 @@ struct Gen {
          "  u64 ub[EVQL_NUPD];\n  bool uc[EVQL_NUPD];\n};\n\n";
   }
 
-  void eval_row() {
-    // string literals used by the row function are declared in front of it
+  // emits one row function through `body`; the string literals it uses are declared in
+  // front of it as evql_slit<lit_base + i>.  Returns their number.
+  template <typename Body>
+  size_t row_function(size_t lit_base, Body body) {
     const std::string before = s.str();
     s.str("");
     Emitter em;
-    eval_row_body(em);
+    em.lit_base = lit_base;
+    body(em);
     const std::string fn = s.str();
     s.str("");
     s << before;
     for (size_t i = 0; i < em.string_literals.size(); ++i) {
       const std::string& l = em.string_literals[i];
-      s << "__device__ const u8 evql_slit" << i << "[" << (l.empty() ? 1 : l.size()) << "] = {";
+      s << "__device__ const u8 evql_slit" << (lit_base + i) << "[" << (l.empty() ? 1 : l.size())
+        << "] = {";
       for (size_t k = 0; k < l.size(); ++k) s << (k ? "," : "") << unsigned((unsigned char) l[k]);
       if (l.empty()) s << "0";
       s << "};\n";
     }
     s << fn;
+    return em.string_literals.size();
   }
 
-  void eval_row_body(Emitter& em) {
-    s << "__device__ __forceinline__ void evql_eval_row(const EvqlArgs& A, const u64 row, "
-         "const bool valid";
-    for (int i = 0; i < NC; ++i) s << ", const u64 r" << i << ", const u32 g" << i;
-    s << ", EvqlRowOut& o) {\n";
-    s << "  bool live = valid;\n";
-    if (kp.has_row_filter) {
-      s << "  live = live && evql_row_filter(A.row_filter, A.row_filter_len, row);\n";
-    }
+  size_t n_literals = 0;  // of evql_eval_row
+  void eval_row() {
+    n_literals = row_function(0, [&](Emitter& em) { eval_row_body(em); });
+  }
+
+  // c<i>: scan column i of the row as the VM types it, from its loaded word r<i>
+  void col_decls() {
     for (int i = 0; i < NC; ++i) {
       const ColAccess& c = kp.cols[i];
       s << "  const " << ctype(c.stype) << " c" << i << " = ";
@@ -202,6 +207,18 @@ struct Gen {
       }
       s << "  (void) c" << i << "; (void) g" << i << ";\n";
     }
+  }
+
+  void eval_row_body(Emitter& em) {
+    s << "__device__ __forceinline__ void evql_eval_row(const EvqlArgs& A, const u64 row, "
+         "const bool valid";
+    for (int i = 0; i < NC; ++i) s << ", const u64 r" << i << ", const u32 g" << i;
+    s << ", EvqlRowOut& o) {\n";
+    s << "  bool live = valid;\n";
+    if (kp.has_row_filter) {
+      s << "  live = live && evql_row_filter(A.row_filter, A.row_filter_len, row);\n";
+    }
+    col_decls();
     em.ind = "    ";
     if (kp.where) {
       s << "  if (live) {\n";
@@ -302,14 +319,16 @@ struct Gen {
     s << "  }\n}\n\n";
   }
 
-  // loads of one tile into x<i>[u][j] / y<i>[u][j]
-  void tile_loads(const char* ind) {
+  // loads of one tile into x<i>[u][j] / y<i>[u][j]; `only`: of these columns alone
+  void tile_loads(const char* ind, const std::vector<bool>* only = nullptr) {
     for (int i = 0; i < NC; ++i) {
+      if (only && !(*only)[i]) continue;
       s << ind << "u64 x" << i << "[EVQL_UNROLL][2]; u32 y" << i << "[EVQL_UNROLL][2];\n";
     }
     s << "#pragma unroll\n" << ind << "for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << ind << "  const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
     for (int i = 0; i < NC; ++i) {
+      if (only && !(*only)[i]) continue;
       const ColAccess& c = kp.cols[i];
       switch (c.mode) {
         case ColAccess::PLAIN64:
@@ -339,11 +358,18 @@ struct Gen {
     s << ind << "}\n";
   }
 
-  // evaluates row (u, j) of the loaded tile into `o`
-  void eval_call(const char* ind, int j) {
+  // evaluates row (u, j) of the loaded tile into `o` (columns outside `only` were not
+  // loaded and read as 0: the caller knows that the row function does not use them)
+  void eval_call(const char* ind, int j, const std::vector<bool>* only = nullptr) {
     s << ind << "evql_eval_row(A, r + " << j << ", (r + " << j << " >= A.row_begin) && (r + " << j
       << " < A.row_end)";
-    for (int i = 0; i < NC; ++i) s << ", x" << i << "[u][" << j << "], y" << i << "[u][" << j << "]";
+    for (int i = 0; i < NC; ++i) {
+      if (only && !(*only)[i]) {
+        s << ", 0ull, 0u";
+        continue;
+      }
+      s << ", x" << i << "[u][" << j << "], y" << i << "[u][" << j << "]";
+    }
     s << ", o);\n";
   }
 
@@ -648,6 +674,194 @@ struct Gen {
       s << "  evql_lds_flush<false>(A, lds);\n";
     }
     s << "}\n\n";
+  }
+
+  // ---- bare scans: SELECT .. WHERE without GROUP BY / aggregates ---------------------------
+  //
+  // The passing rows leave the device in ROW ORDER (a LIMIT above the scan depends on it),
+  // so the hash-ordered scatter machinery above does not apply.  Two passes over the tiles,
+  // no waiting between workgroups (no look-back, no spinning on another workgroup's flag):
+  //
+  //   evql_scan_count  predicate of every row (only the columns WHERE reads are loaded),
+  //                    passing rows per tile -> tile_count[t]; the host scans the counts
+  //   evql_scan_emit   over a contiguous tile range (a window): predicate again, rank of
+  //                    every passing row inside its tile (row order is (u, tid, j): one
+  //                    ballot per (u, j), mbcnt for the lanes below, wave totals through
+  //                    LDS), select expressions of the passing rows staged in LDS in rank
+  //                    order, then the tile's run stored at tile_offset[t] - window_base:
+  //                    consecutive lanes store consecutive elements, 16 bytes per lane
+  //
+  // Output per select expression: one u64 word (strings: length << 40 | position) and, for
+  // expressions that can be NULL, one tag byte per passing row.
+  void bare_scan_kernels() {
+    const int NOUT = int(kp.scan_out.size());
+    std::vector<bool> where_cols(size_t(NC), false);
+    if (kp.where) {
+      std::vector<uint32_t> used;
+      expr_inputs(kp.where, &used);
+      for (uint32_t u : used) {
+        if (u < uint32_t(NC)) where_cols[u] = true;
+      }
+    }
+    int n_nullable = 0;
+    for (int k = 0; k < NOUT; ++k) n_nullable += kp.scan_out_nullable[k] ? 1 : 0;
+    // how many unroll steps are staged in LDS at once: the whole tile when its values fit
+    // 48 KiB (runs of up to a tile per store phase, two barriers per tile), else one step
+    const int stage_steps =
+        uint64_t(kp.tile_rows()) * uint64_t(8 * NOUT + n_nullable) <= 48 * 1024 ? kp.unroll : 1;
+    s << "#define EVQL_NOUT " << NOUT << "\n";
+    s << "#define EVQL_NWAVE (EVQL_BLOCK / 64)\n";
+    s << "#define EVQL_STAGE_STEPS " << stage_steps << "\n";
+    s << "#define EVQL_STAGE_ROWS (EVQL_STAGE_STEPS * EVQL_BLOCK * 2)\n";
+    s << "static_assert(EVQL_UNROLL * EVQL_NWAVE <= 64, \"one wave scans the wave totals of a tile\");\n";
+    // (host mirror: HostScanArgs in bare_scan.cc)
+    s << "struct EvqlScanArgs {\n"
+         "  const u64* tile_offset;  // [ntiles + 1]: passing rows in front of tile t of the scan\n"
+         "  u64 t0, t1;              // the window: tiles [t0, t1)\n"
+         "  u64 window_base;         // tile_offset[t0]\n"
+         "  u64 window_rows;         // tile_offset[t1] - window_base: rows of every output array\n"
+         "  u64* words;              // [EVQL_NOUT][window_rows]\n"
+         "  u8* tags;                // [EVQL_NOUT][window_rows], written for nullable outputs only\n"
+         "};\n\n";
+    // values of the select list for one passing row
+    row_function(n_literals, [&](Emitter& em) {
+      s << "__device__ __forceinline__ void evql_scan_select(const EvqlArgs& A, const u64 row";
+      for (int i = 0; i < NC; ++i) s << ", const u64 r" << i << ", const u32 g" << i;
+      s << ", u64 (&w)[EVQL_NOUT], u32 (&q)[EVQL_NOUT]) {\n";
+      col_decls();
+      em.ind = "  ";
+      for (int k = 0; k < NOUT; ++k) {
+        const ExprPtr& e = kp.scan_out[k];
+        if (e->kind == Expr::INPUT && e->type == EVQL_T_STRING) {
+          // a string travels as the (length << 40 | position) word of its bytes
+          s << "  w[" << k << "] = A.col[" << e->input << "].strpos[row]; q[" << k << "] = g" << e->input
+            << ";\n";
+          continue;
+        }
+        Val v = em.emit(e);
+        s << em.o.str();
+        em.o.str("");
+        s << "  w[" << k << "] = " << Emitter::as_bits(v) << "; q[" << k << "] = " << v.g << ";\n";
+      }
+      s << "}\n\n";
+    });
+    // n elements of 8 bytes from LDS to out[at, at + n): an element in front of the first
+    // 16-byte boundary and one behind the last go alone, the pairs between them as 16 bytes
+    // per lane.  Nothing is stored at or behind out[cap].
+    s << "__device__ __forceinline__ void evql_run_store(u64* out, const u64 at, const u64 cap, const u64* src, "
+         "u32 n) {\n"
+         "  typedef u64 evql_u64x2 __attribute__((ext_vector_type(2)));\n"
+         "  if (at >= cap) return;\n"
+         "  if ((u64) n > cap - at) n = (u32) (cap - at);\n"
+         "  u64* const dst = out + at;\n"
+         "  const u32 head = (n > 0 && ((u64) dst & 8ull)) ? 1u : 0u;\n"
+         "  const u32 pairs = (n - head) >> 1;\n"
+         "  if (threadIdx.x == 0 && head) dst[0] = src[0];\n"
+         "  for (u32 i = threadIdx.x; i < pairs; i += EVQL_BLOCK) {\n"
+         "    evql_u64x2 v;\n    v.x = src[head + 2 * i];\n    v.y = src[head + 2 * i + 1];\n"
+         "    *reinterpret_cast<evql_u64x2*>(dst + head + 2 * i) = v;\n  }\n"
+         "  if (threadIdx.x == 0 && ((n - head) & 1u)) dst[n - 1] = src[n - 1];\n"
+         "}\n\n";
+
+    // pass 1
+    s << "extern \"C\" __global__ void __launch_bounds__(EVQL_BLOCK) evql_scan_count(const EvqlArgs A, "
+         "u32* tile_count) {\n";
+    s << "  const u32 tid = threadIdx.x;\n";
+    s << "  __shared__ u32 wsum[EVQL_NWAVE];\n";
+    s << "  for (u64 t = blockIdx.x; t < A.ntiles; t += gridDim.x) {\n";
+    s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_loads("    ", &where_cols);
+    s << "    u32 cnt = 0;\n";
+    s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
+    s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
+    s << "      EvqlRowOut o;\n";
+    for (int j = 0; j < 2; ++j) {
+      eval_call("      ", j, &where_cols);
+      s << "      cnt += (u32) __popcll(__ballot(o.live));\n";
+    }
+    s << "    }\n";
+    s << "    if ((tid & 63u) == 0) wsum[tid >> 6] = cnt;\n";
+    s << "    __syncthreads();\n";
+    s << "    if (tid == 0) {\n      u32 total = 0;\n";
+    s << "      for (u32 k = 0; k < EVQL_NWAVE; ++k) total += wsum[k];\n";
+    s << "      tile_count[t] = total;\n    }\n";
+    s << "    __syncthreads();\n";
+    s << "  }\n}\n\n";
+
+    // pass 2
+    s << "extern \"C\" __global__ void __launch_bounds__(EVQL_BLOCK) evql_scan_emit(const EvqlArgs A, "
+         "const EvqlScanArgs S) {\n";
+    s << "  const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;\n";
+    s << "  __shared__ u64 sw[EVQL_NOUT * EVQL_STAGE_ROWS];\n";
+    if (n_nullable) s << "  __shared__ u8 sq[" << n_nullable << " * EVQL_STAGE_ROWS];\n";
+    // exclusive prefix of the passing rows of (step u, wave) in row order; [last] = the tile's
+    s << "  __shared__ u32 wpre[EVQL_UNROLL * EVQL_NWAVE + 1];\n";
+    s << "  for (u64 t = S.t0 + blockIdx.x; t < S.t1; t += gridDim.x) {\n";
+    // (a tile without passing rows -- selective predicates -- is not read again)
+    s << "    const u64 dst0 = S.tile_offset[t] - S.window_base;\n";
+    s << "    if (S.tile_offset[t + 1] == S.tile_offset[t]) continue;\n";
+    s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_loads("    ");
+    s << "    u32 live = 0;  // bit 2u + j: row (u, j) of this lane passes\n";
+    s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
+    s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
+    s << "      EvqlRowOut o;\n";
+    s << "      u32 wcnt = 0;\n";
+    for (int j = 0; j < 2; ++j) {
+      eval_call("      ", j);
+      s << "      live |= o.live ? (1u << (2 * u + " << j << ")) : 0u;\n";
+      s << "      wcnt += (u32) __popcll(__ballot(o.live));\n";
+    }
+    s << "      if (lane == 0) wpre[u * EVQL_NWAVE + wave] = wcnt;\n";
+    s << "    }\n    __syncthreads();\n";
+    s << "    if (wave == 0) {\n";
+    s << "      const u32 v = lane < EVQL_UNROLL * EVQL_NWAVE ? wpre[lane] : 0u;\n";
+    s << "      u32 incl = v;\n";
+    s << "#pragma unroll\n      for (int d = 1; d < 64; d <<= 1) { const u32 x = __shfl_up(incl, d, 64); "
+         "if ((int) lane >= d) incl += x; }\n";
+    s << "      if (lane < EVQL_UNROLL * EVQL_NWAVE) wpre[lane] = incl - v;\n";
+    s << "      if (lane == EVQL_UNROLL * EVQL_NWAVE - 1) wpre[EVQL_UNROLL * EVQL_NWAVE] = incl;\n";
+    s << "    }\n    __syncthreads();\n";
+    s << "#pragma unroll\n    for (int u0 = 0; u0 < EVQL_UNROLL; u0 += EVQL_STAGE_STEPS) {\n";
+    s << "      const u32 g0 = wpre[u0 * EVQL_NWAVE], g1 = wpre[(u0 + EVQL_STAGE_STEPS) * EVQL_NWAVE];\n";
+    s << "#pragma unroll\n      for (int u = u0; u < u0 + EVQL_STAGE_STEPS; ++u) {\n";
+    s << "        const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
+    s << "        const bool l0 = (live >> (2 * u)) & 1u, l1 = (live >> (2 * u + 1)) & 1u;\n";
+    s << "        const u64 b0 = __ballot(l0), b1 = __ballot(l1);\n";
+    s << "        u32 rank = wpre[u * EVQL_NWAVE + wave] - g0;\n";
+    s << "        rank = __builtin_amdgcn_mbcnt_hi((u32) (b0 >> 32), __builtin_amdgcn_mbcnt_lo((u32) b0, rank));\n";
+    s << "        rank = __builtin_amdgcn_mbcnt_hi((u32) (b1 >> 32), __builtin_amdgcn_mbcnt_lo((u32) b1, rank));\n";
+    for (int j = 0; j < 2; ++j) {
+      s << "        if (l" << j << ") {\n";
+      s << "          u64 w[EVQL_NOUT]; u32 q[EVQL_NOUT];\n";
+      s << "          evql_scan_select(A, r + " << j;
+      for (int i = 0; i < NC; ++i) s << ", x" << i << "[u][" << j << "], y" << i << "[u][" << j << "]";
+      s << ", w, q);\n";
+      int nk = 0;
+      for (int k = 0; k < NOUT; ++k) {
+        s << "          sw[" << k << " * EVQL_STAGE_ROWS + rank] = w[" << k << "];\n";
+        if (kp.scan_out_nullable[k]) {
+          s << "          sq[" << nk++ << " * EVQL_STAGE_ROWS + rank] = (u8) (q[" << k << "] & 1u);\n";
+        }
+      }
+      s << "          rank += 1;\n        }\n";
+    }
+    s << "      }\n      __syncthreads();\n";
+    s << "      const u32 n = g1 - g0;\n";
+    s << "      const u64 at = dst0 + g0;\n";
+    {
+      int nk = 0;
+      for (int k = 0; k < NOUT; ++k) {
+        s << "      evql_run_store(S.words + " << k << " * S.window_rows, at, S.window_rows, sw + " << k
+          << " * EVQL_STAGE_ROWS, n);\n";
+        if (kp.scan_out_nullable[k]) {
+          s << "      for (u32 i = tid; i < n && at + i < S.window_rows; i += EVQL_BLOCK) S.tags[" << k
+            << " * S.window_rows + at + i] = sq[" << nk++ << " * EVQL_STAGE_ROWS + i];\n";
+        }
+      }
+    }
+    s << "      __syncthreads();\n";
+    s << "    }\n  }\n}\n\n";
   }
 
   // ---- predicate of every row (nested scans, see KernelPlan::where_rows_kernel) -------------
@@ -1105,8 +1319,12 @@ std::string generate_kernel_source(const KernelPlan& kp) {
   Gen g(kp);
   g.prologue();
   g.eval_row();
-  g.scan_kernel();
-  if (kp.partitioned) g.partition_kernels();
+  if (kp.bare_scan) {
+    g.bare_scan_kernels();
+  } else {
+    g.scan_kernel();
+    if (kp.partitioned) g.partition_kernels();
+  }
   if (kp.where_rows_kernel) g.where_rows_kernel();
   return g.s.str();
 }

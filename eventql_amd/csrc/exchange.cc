@@ -1250,6 +1250,7 @@ int evql_query_exchange(evql_query_t* q, evql_exchange_t* x, int mode) {
   if (mode != EVQL_EXCHANGE_GATHER_ALL && mode != EVQL_EXCHANGE_BY_OWNER) {
     return fail(EVQL_EARG, "bad exchange mode");
   }
+  if (q->kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
   try {
     if (hipSetDevice(q->ctx->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
     Status st = exchange(q, x, mode);

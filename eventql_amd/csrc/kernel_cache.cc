@@ -133,7 +133,12 @@ Status compile_kernel(evql_ctx* ctx, const std::string& source, Module* out, boo
       out->code_size = code.size();
       HIP_TRY(hipModuleLoadData(&out->mod, code.data()));
     }
-    HIP_TRY(hipModuleGetFunction(&out->fn, out->mod, "evql_scan_agg"));
+    if (source.find("evql_scan_emit") != std::string::npos) {  // a bare scan
+      HIP_TRY(hipModuleGetFunction(&out->fn_scan_count, out->mod, "evql_scan_count"));
+      HIP_TRY(hipModuleGetFunction(&out->fn_scan_emit, out->mod, "evql_scan_emit"));
+    } else {
+      HIP_TRY(hipModuleGetFunction(&out->fn, out->mod, "evql_scan_agg"));
+    }
     if (source.find("evql_part_aggregate") != std::string::npos) {
       out->fn_count = nullptr;  // (absent from the fused form, KernelPlan::part_fused)
       if (source.find("evql_part_count(") != std::string::npos) {

@@ -283,7 +283,19 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
   }
   if (nested && (plan->row_begin || plan->row_end)) return unsup("row range on a nested scan");
   if (plan->n_scan_columns > EVQL_MAX_COLS_HOST) return unsup("too many scan columns");
-  if (plan->n_select == 0) return unsup("bare scans are not lowered (no GROUP BY / aggregate)");
+  // a plan with neither group expressions nor a select list is a bare scan of its scan
+  // select list: FastCSTableScan::nextBatch / CSTableScan NO_AGGREGATION straight to the caller
+  const bool bare = plan->n_select == 0 && plan->n_group == 0 && plan->n_scan_select > 0;
+  if (plan->n_select == 0 && !bare) {
+    return unsup("bare scans are not lowered (no GROUP BY / aggregate)");
+  }
+  if (bare) {
+    if (plan->group_mode == EVQL_MODE_PARTIAL) {
+      return Status::error(EVQL_EARG, "a bare scan has no partial form");
+    }
+    if (within) return unsup("WITHIN RECORD bare scans are not lowered");
+    if (plan->n_scan_select > kMaxEmitCols) return unsup("too many output columns in a bare scan");
+  }
 
   // ---- scan columns --------------------------------------------------------------
   for (uint32_t i = 0; i < plan->n_scan_columns; ++i) {
@@ -555,6 +567,28 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
     if (q->scan_select[i].is_aggregate) return unsup("aggregate in the scan select list");
     if (!strings_lowerable(q->scan_select[i].call)) return unsup("string expression is not lowerable");
     scan_out.push_back(q->scan_select[i].call);
+  }
+  if (bare) {
+    // the scan select list is the output: every expression is evaluated by the kernel for
+    // the passing rows.  A string leaves as the bytes of a bare column reference.
+    for (const ExprPtr& e : scan_out) {
+      if (e->type == EVQL_T_NIL) return unsup("NIL output column in a bare scan");
+      std::vector<uint32_t> ins;
+      expr_inputs(e, &ins);
+      for (uint32_t in : ins) {
+        if (in >= kp.cols.size()) return Status::error(EVQL_EARG, "invalid input index");
+      }
+      if (e->type == EVQL_T_STRING) {
+        // (a cell of the Dremel scan is a boxed SValue whose tag byte can carry STAG_INLINE,
+        // results.cc group_select_inputs: not reproduced by the device packer)
+        if (nested) return unsup("string output columns of a nested bare scan are not lowered");
+        kp.cols[e->input].string_bytes = true;
+      }
+      mark_string_bytes(e, &kp.cols);
+      kp.scan_out_nullable.push_back(expr_may_be_null(e, kp.cols));
+    }
+    kp.bare_scan = true;
+    kp.scan_out = scan_out;
   }
   q->group.resize(plan->n_group);
   for (uint32_t i = 0; i < plan->n_group; ++i) {

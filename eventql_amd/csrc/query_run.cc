@@ -110,9 +110,10 @@ static Status compile_plan_kernels(evql_query* q) {
   while (q->kp.unroll > 1) {
     // (the kernels that hold a tile in registers: the fused scan and, for partitioned
     // plans, count and scatter -- only the latter run then)
+    // (a bare scan: its count and emit kernels)
     int scratch = 0;
-    hipFunction_t fns[3] = {q->kp.partitioned ? nullptr : q->module.fn, q->module.fn_count,
-                            q->module.fn_scatter};
+    hipFunction_t fns[5] = {q->kp.partitioned ? nullptr : q->module.fn, q->module.fn_count,
+                            q->module.fn_scatter, q->module.fn_scan_count, q->module.fn_scan_emit};
     for (hipFunction_t f : fns) {
       int sc = 0;
       if (f && hipFuncGetAttribute(&sc, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) == hipSuccess) {
@@ -127,8 +128,8 @@ static Status compile_plan_kernels(evql_query* q) {
   }
   // persistent grid: one wave of workgroups per CU slot
   int per_cu = 1;
-  hipError_t oe = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, q->module.fn,
-                                                                     q->kp.block, 0);
+  hipError_t oe = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, q->kp.bare_scan ? q->module.fn_scan_emit : q->module.fn, q->kp.block, 0);
   if (oe != hipSuccess || per_cu < 1) per_cu = 1;
   if (per_cu > 8) per_cu = 8;
   q->grid = ctx->num_cus * per_cu;
@@ -254,6 +255,7 @@ Status query_prepare(evql_query* q) {
   }
   Status st = compile_plan_kernels(q);
   if (!st.ok()) return st;
+  if (q->kp.bare_scan) bare_configure(q);
   // (two allocations on purpose: with the status words and the counters in one 128-byte
   // line -- tried, to read both back with one copy -- the scan kernel's per-tile poll of
   // status[0] shared its line with the counter atomics: config 3 over 16-bit pages
@@ -411,6 +413,7 @@ void fill_host_args(evql_query* q, HostArgs* ap) {
 
 Status query_launch(evql_query* q) {
   evql_ctx* ctx = q->ctx;
+  if (q->kp.bare_scan) return bare_launch(q);
   if (!q->probed && q->groups_hint == 0 && q->kp.key_mode != KEY_NONE && !q->within_record) {
     q->probed = true;
     Status st = probe_cardinality(q);
@@ -628,6 +631,7 @@ Status query_records_view(evql_query* q, RecordsView* v) {
 
 Status query_finish(evql_query* q) {
   if (!q->launched) return Status::error(EVQL_EARG, "query was not launched");
+  if (q->kp.bare_scan) return bare_finish(q);
   evql_ctx* ctx = q->ctx;
   for (int attempt = 0; attempt < 12; ++attempt) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -878,6 +882,7 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
 // GroupByMergeExpression (groupby.cc:528-637)
 Status query_reset(evql_query* q) {
   evql_ctx* ctx = q->ctx;
+  if (q->kp.bare_scan) return bare_reset(q);
   const KernelPlan& kp = q->kp;
   if (!q->d_gtab) {
     uint64_t want = kp.key_mode == KEY_NONE ? 8 : std::max<uint64_t>(q->groups_hint * 4, 1 << 16);

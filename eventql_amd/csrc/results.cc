@@ -679,6 +679,7 @@ static void save_state(const evql_query* q, const AggPlan& a, const uint64_t* st
 // ---------------------------------------------------------------------------
 Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,
                        uint64_t offset) {
+  if (q->kp.bare_scan) return bare_set_limit(q, n, limit, offset);
   if (q->group_mode == EVQL_MODE_PARTIAL) {
     return Status::error(EVQL_EARG, "ORDER BY / LIMIT above a partial aggregate");
   }
@@ -906,6 +907,7 @@ static Status order_fetched(evql_query* q) {
 }
 
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows) {
+  if (q->kp.bare_scan) return bare_next_batch(q, max_rows, cols, nrows);
   if (!q->executed) return Status::error(EVQL_EARG, "execute() was not called");
   if (!q->fetched) {
     Status st = fetch_results(q);

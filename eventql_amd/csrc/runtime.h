@@ -59,6 +59,8 @@ struct Module {
   hipFunction_t fn_count = nullptr, fn_scatter = nullptr, fn_aggregate = nullptr;
   hipFunction_t fn_refine = nullptr;  // second scatter level (part_bits > 8)
   hipFunction_t fn_where = nullptr;   // evql_where_rows (nested scans, mixed-depth WHERE)
+  // bare scans (KernelPlan::bare_scan): instead of `fn`
+  hipFunction_t fn_scan_count = nullptr, fn_scan_emit = nullptr;
   size_t code_size = 0;
 };
 
@@ -376,6 +378,31 @@ struct evql_query {
   // EVQL_MODE_PARTIAL with count_distinct: the distinct values of every group, per
   // aggregate, read back from the HBM pair set; key = (identity, identity 2 | NULL flag)
   std::vector<std::map<std::pair<uint64_t, uint64_t>, std::vector<uint64_t>>> distinct_values;
+  // Bare scans (kp.bare_scan, bare_scan.cc).  execute counts the passing rows of every
+  // tile; next_batch emits and packs one WINDOW of consecutive tiles at a time -- the result
+  // can be as large as the table and is never held whole -- into demit's pinned columns and
+  // hands out slices of it.
+  struct BareScan {
+    uint64_t window_rows = 0;         // most passing rows of one window (>= one tile)
+    uint64_t ntiles = 0;
+    evql::DevBuf<uint32_t> d_tile_count;
+    evql::DevBuf<uint64_t> d_tile_off;  // [ntiles + 1] exclusive scan of the counts
+    uint64_t tiles_cap = 0;
+    bool counted_on_device = false;
+    std::vector<uint64_t> tile_off;   // host copy
+    // passing rows are numbered in row order; [lo, hi) of them are the result (LIMIT / OFFSET)
+    uint64_t lo = 0, hi = 0, pos = 0;  // pos: the next row next_batch hands out
+    uint64_t win_base = 0, win_rows = 0;  // rows [win_base, win_base + win_rows) are staged
+    evql::DevBuf<uint64_t> d_words;   // [column][win_rows] value words of the window
+    evql::DevBuf<uint8_t> d_tags;
+    uint64_t stage_cap = 0;           // elements d_words / d_tags hold
+    double emit_ms = 0;               // device time of the window kernels so far
+    // the heartbeat of the last evql_query_execute: the window kernels of next_batch beat
+    // it too (a scan's device work continues behind execute)
+    int (*hb)(void*) = nullptr;
+    void* hb_user = nullptr;
+    uint64_t windows = 0;
+  } bare;
   // ORDER BY .. LIMIT fused above the GROUP BY (evql_query_set_order)
   std::vector<evql::LoweredProgram> order;  // over the select list
   std::vector<bool> order_desc;
@@ -465,6 +492,14 @@ Status query_dense_into_table(evql_query* q);
 Status query_reserve_groups(evql_query* q, uint64_t extra);
 Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, uint64_t n);
 void fill_host_args(evql_query* q, HostArgs* ap);
+
+// bare_scan.cc: the life cycle of a bare-scan query (kp.bare_scan)
+void bare_configure(evql_query* q);
+Status bare_launch(evql_query* q);
+Status bare_finish(evql_query* q);
+Status bare_reset(evql_query* q);
+Status bare_set_limit(evql_query* q, uint32_t n_specs, int64_t limit, uint64_t offset);
+Status bare_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
 
 // results.cc
 Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,

@@ -423,6 +423,25 @@ typedef struct {
   const evql_program_t* group_exprs; /* n_group == 0 => one global group */
   uint32_t n_group;
 
+  /* n_select == 0 && n_group == 0 && n_scan_select > 0: a BARE SCAN (FastCSTableScan::
+   * nextBatch / CSTableScan NO_AGGREGATION handed straight to the caller).  The output
+   * columns are the scan_select programs; one row per row of [row_begin, row_end) -- per
+   * flattened row of an EVQL_SCAN_NESTED scan -- that passes the row filter and `where`,
+   * in ASCENDING ROW ORDER.  Numeric / bool / timestamp expressions (IF with real
+   * branches: a zero divisor raises only for passing rows that reach it) are evaluated
+   * on the device; a string leaves as the bytes of a bare column reference
+   * (EVQL_ENOTSUP: string-producing select expressions, string outputs of a nested scan,
+   * EVQL_SCAN_NESTED_WITHIN_RECORD).  EVQL_MODE_PARTIAL is EVQL_EARG: the reference has
+   * no partial form of a scan.  The result can be as large as the table and is never held
+   * whole: evql_query_execute counts the passing rows, evql_query_next_batch emits one
+   * WINDOW of consecutive row tiles at a time -- at most 256 MiB of staging on the device
+   * and as much pinned host memory; the environment variable EVQL_SCAN_WINDOW_ROWS, read
+   * by evql_query_create, sets the window in rows instead (tests, tuning; never less than
+   * one tile) -- and hands out slices of it.  An error of a select expression surfaces
+   * from the next_batch call whose window holds the row.  stats: rows_scanned /
+   * rows_passed as for grouped plans, num_groups 0.  evql_query_export_groups /
+   * import_groups / export_pairs / import_pairs / partial_view / exchange answer
+   * EVQL_EARG on a bare scan. */
   const evql_program_t* select_exprs;
   uint32_t n_select;
 
@@ -484,7 +503,10 @@ typedef int (*evql_heartbeat_fn)(void* user);
  * to completion on the device.  `hb` is called before the launch, every 5 ms while the
  * kernels run (the host polls the stream) and once after them -- the reference beats
  * once per input batch (groupby.cc:100-105); non-zero = stop: honoured when the
- * kernels have drained, execute then fails with EVQL_ERUNTIME "query aborted". */
+ * kernels have drained, execute then fails with EVQL_ERUNTIME "query aborted".  A bare scan
+ * (evql_plan_desc_t) does its emitting in evql_query_next_batch: `hb` is kept and called
+ * there as well -- once per window and every 5 ms while the window's kernels run -- so
+ * `user` must stay valid until the query is drained, executed again or destroyed. */
 int evql_query_execute(evql_query_t* q, evql_heartbeat_fn hb, void* user);
 
 /* asynchronous form used by benchmarks: enqueue the kernels on the context
@@ -709,6 +731,11 @@ typedef struct {
   evql_program_t expr;
   uint32_t descending;
 } evql_sort_spec_t;
+/* On a bare scan (n_select == 0 && n_group == 0): n_specs == 0 with limit >= 0 is
+ * LimitExpression over the ordered rows -- tiles in front of `offset` are skipped by their
+ * counts, tiles behind offset + limit are never emitted; any sort spec answers EVQL_ENOTSUP
+ * "ORDER BY over a bare scan is not fused" (the caller keeps its OrderByExpression above
+ * the operator). */
 int evql_query_set_order(evql_query_t* q, const evql_sort_spec_t* specs,
                          uint32_t n_specs, int64_t limit, uint64_t offset);
 
@@ -764,7 +791,9 @@ int evql_lsm_chain_filter(evql_lsm_chain_t* ch, int idx,
  * Every scan mode: PartitionCursor builds FastCSTableScan for NO_AGGREGATION statements
  * (EVQL_SCAN_FLAT) and CSTableScan for the others (EVQL_SCAN_NESTED[_WITHIN_RECORD]),
  * :42-50, 197-217, and calls setFilter on either; the chain's filters hold one bit per
- * record.  EVQL_ENOTSUP: a bare scan over more than one table, and whatever
+ * record.  A bare scan over a chain of ONE table is lowered and takes its row filter from
+ * the chain.  EVQL_ENOTSUP: a bare scan over more than one table ("bare scan over a chain
+ * of tables": its rows would have to be concatenated in scan order), and whatever
  * evql_query_create refuses for one table under a row filter.
  */
 int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch,
