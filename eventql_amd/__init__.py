@@ -66,6 +66,8 @@ def lib():
     L.evql_table_column_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(K.ColumnInfo)]
     L.evql_table_image_size.restype = C.c_uint64
     L.evql_table_image_size.argtypes = [C.c_void_p]
+    L.evql_table_device_bytes.restype = C.c_uint64
+    L.evql_table_device_bytes.argtypes = [C.c_void_p]
     L.evql_table_download_image.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.evql_table_generate.argtypes = [C.c_void_p, C.POINTER(K.SynthSpec), C.POINTER(C.c_void_p)]
     L.evql_table_from_device_columns.argtypes = [C.c_void_p, C.POINTER(K.ColumnSpec), C.c_int,
@@ -348,6 +350,11 @@ class Table:
         buf = C.create_string_buffer(n)
         _check(lib().evql_table_download_image(self.h, buf, n))
         return buf.raw
+
+    def device_bytes(self):
+        """HBM the table holds now: the image plus everything cached on it (decoded columns,
+        narrow copies, dictionaries, flattened nested columns)"""
+        return lib().evql_table_device_bytes(self.h)
 
     def query(self, plan):
         q = C.c_void_p()

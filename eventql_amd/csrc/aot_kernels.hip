@@ -2693,6 +2693,58 @@ __global__ void __launch_bounds__(kBlock) k_wr_bitpack(u8* image, const u64* pag
   *reinterpret_cast<u32*>(dst) = word;
 }
 
+// A required UINT64_PLAIN column of the image (65,536 values per page, pages wherever the
+// file put them) once more as the bit-packed pages k_wr_bitpack writes, of width 8 / 16 /
+// 32, for values known to fit `bits`.  One wave per block of 128 values: lane L reads
+// values 2L and 2L + 1 with one 16-byte load (1 KiB contiguous per wave and block), the
+// lanes exchange the low words so that lane j holds output word j of the block -- word w
+// of libsimdcomp lane l sits at index 4w + l and packs the values 4k + l,
+// k = w * 32 / bits .. -- and the block leaves as one contiguous store of 16 * bits bytes.
+__global__ void __launch_bounds__(kBlock) k_narrow_plain64(const u8* image, const u64* src_pages,
+                                                           u8* dst, const u64* dst_pages, u64 n,
+                                                           u32 bits) {
+  const u32 lane = threadIdx.x & 63u;
+  const u64 wave = ((u64) blockIdx.x * kBlock + threadIdx.x) >> 6;
+  const u64 nwaves = ((u64) gridDim.x * kBlock) >> 6;
+  const u64 nblocks = (n + 127) / 128;
+  const u32 w = lane >> 2, l = lane & 3u;
+  for (u64 blk = wave; blk < nblocks; blk += nwaves) {
+    const u64 r = blk * 128 + 2 * lane;
+    u32 x0 = 0, x1 = 0;
+    if (r < n) {  // (r is even: r + 1 lies in the same source page)
+      const u8* p = image + src_pages[r / kPlain64PageValues] + ((r % kPlain64PageValues) << 3);
+      const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
+      x0 = q.x;
+      x1 = r + 1 < n ? q.z : 0u;
+    }
+    const u64 page = blk >> 10;
+    u8* out = dst + dst_pages[page] + (page == 0 ? 4 : 0) + (blk & 1023ull) * (16 * bits);
+    if (bits == 32) {  // word 4w + l = value 4w + l
+      // (`out` is 4 mod 8 behind the page header: evql_u32x2 is declared aligned(4))
+      static_assert(alignof(evql_u32x2) == 4, "dword-aligned 8-byte store");
+      evql_u32x2 o;
+      o.x = x0;
+      o.y = x1;
+      *reinterpret_cast<evql_u32x2*>(out + 8 * lane) = o;
+    } else if (bits == 16) {  // values 8w + l and 8w + 4 + l
+      const int a = (int) (4 * w + (l >> 1));
+      const u32 a0 = __shfl(x0, a, 64), a1 = __shfl(x1, a, 64);
+      const u32 b0 = __shfl(x0, a + 2, 64), b1 = __shfl(x1, a + 2, 64);
+      const u32 va = (l & 1u) ? a1 : a0, vb = (l & 1u) ? b1 : b0;
+      *reinterpret_cast<u32*>(out + 4 * lane) = (va & 0xffffu) | (vb << 16);
+    } else {  // 8 bits: 32 words, values 16w + l + 4m, m = 0 .. 3
+      const int a = (int) (8 * (w & 7u) + (l >> 1));
+      u32 word = 0;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const u32 m0 = __shfl(x0, a + 2 * m, 64), m1 = __shfl(x1, a + 2 * m, 64);
+        word |= (((l & 1u) ? m1 : m0) & 0xffu) << (8 * m);
+      }
+      if (lane < 32) *reinterpret_cast<u32*>(out + 4 * lane) = word;
+    }
+  }
+}
+
 // UInt64PageWriter / UInt32PageWriter: value i at stream byte i * width
 __global__ void __launch_bounds__(kBlock) k_wr_plain(u8* image, const u64* pages,
                                                      const u64* dense, u64 n, u32 width) {
@@ -2986,6 +3038,17 @@ hipError_t launch_wr_compact(const uint64_t* values, const uint8_t* nulls,
   hipLaunchKernelGGL(k_wr_compact, dim3((unsigned) ntiles), dim3(kBlock), 0, s,
                      (const u64*) values, nulls, (const u64*) tile_offsets, (u64) nrows,
                      (u64*) dense);
+  return hipGetLastError();
+}
+
+hipError_t launch_narrow_plain64(const uint8_t* image, const uint64_t* src_pages, uint8_t* dst,
+                                 const uint64_t* dst_pages, uint64_t n, uint32_t bits,
+                                 hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const u64 nblocks = (n + 127) / 128;  // one wave each, grid-stride
+  hipLaunchKernelGGL(k_narrow_plain64, dim3(grid_for(nblocks * 64, kBlock, 16384)), dim3(kBlock), 0,
+                     s, (const u8*) image, (const u64*) src_pages, (u8*) dst,
+                     (const u64*) dst_pages, (u64) n, (u32) bits);
   return hipGetLastError();
 }
 

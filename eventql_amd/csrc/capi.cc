@@ -1,4 +1,5 @@
 // capi.cc -- the extern "C" surface declared in include/evql_gpu.h.
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <memory>
@@ -149,6 +150,42 @@ int evql_table_column_info(const evql_table_t* t, int idx, evql_column_info_t* o
 }
 
 uint64_t evql_table_image_size(const evql_table_t* t) { return t->image_len; }
+
+uint64_t evql_table_device_bytes(const evql_table_t* t) {
+  uint64_t total = 0;
+  auto add = [&](const void* p) {
+    size_t n = 0;
+    if (p && hipMemPtrGetInfo(const_cast<void*>(p), &n) == hipSuccess) total += n;
+  };
+  add(t->d_image);
+  for (const auto& v : t->d_pages) {
+    for (const uint64_t* p : v) add(p);
+  }
+  for (const auto& kv : t->materialized) {
+    const MaterializedColumn& m = kv.second;
+    add(m.d_values);
+    add(m.d_tags);
+    add(m.d_strpos);
+    add(m.d_packed);
+    add(m.d_packed_pages);
+  }
+  for (const auto& kv : t->dicts) {
+    add(kv.second.d_codes);
+    add(kv.second.d_code_pages);
+    add(kv.second.d_entries);
+  }
+  for (const auto& kv : t->nested_cache) {
+    add(kv.second.d_values.p);
+    add(kv.second.d_hash.p);
+    add(kv.second.d_packed.p);
+    add(kv.second.d_packed_pages.p);
+  }
+  for (const auto& kv : t->leaf_cache) {
+    add(kv.second.levels.p);
+    add(kv.second.rec_offsets.p);
+  }
+  return total;
+}
 
 int evql_table_download_image(const evql_table_t* t, void* dst, uint64_t len) {
   if (len > t->image_len) len = t->image_len;
@@ -712,9 +749,17 @@ int evql_query_next_batch(evql_query_t* q, size_t max_rows, evql_column_buf_t* c
 int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out) {
   *out = q->stats;
   uint64_t bytes = 0;
+  // per column what the kernel streams: the file's payload, or the narrow copy the table
+  // keeps of it (LEB128 / PLAIN columns as bit-packed pages) where that is smaller
+  auto column_bytes = [](const evql_query* p, const ColAccess& c) -> uint64_t {
+    const uint64_t file = p->table->payload_bytes[c.layout_index];
+    if (!c.packed || p->nested) return file;
+    const uint64_t copy = 4 + 16ull * c.bits * ((p->table->layout.num_rows + 127) / 128);
+    return std::min(file, copy);
+  };
   // (a dictionary-coded key counts as the string column it stands for)
   for (const auto& c : q->within_record ? q->wr_cols : q->rplan().cols) {
-    bytes += q->table->payload_bytes[c.layout_index];
+    bytes += column_bytes(q, c);
   }
   // scaled to the scanned row range; + result bytes (key + 8 B per aggregate)
   const uint64_t nrows = q->table->layout.num_rows;
@@ -723,7 +768,7 @@ int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out) {
     bytes = uint64_t(double(bytes) * double(q->stats.rows_scanned) / double(nrows));
   }
   for (const evql_query* part : q->chain) {  // (chain_merge summed the row counters)
-    for (const auto& c : part->rplan().cols) bytes += part->table->payload_bytes[c.layout_index];
+    for (const auto& c : part->rplan().cols) bytes += column_bytes(part, c);
   }
   bytes += q->stats.num_groups * 8 * (1 + q->kp.aggs.size());
   out->algorithmic_bytes = bytes;

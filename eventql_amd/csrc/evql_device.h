@@ -42,7 +42,7 @@ struct EvqlColArg {
   // byte in the column's logical byte stream (pages laid end to end), or NULL
   const u64* strpos;
   // where `pages` offsets count from: the file image, or the private buffer of a
-  // column the runtime re-encoded (LEB128 -> narrow bit-packed)
+  // column the runtime keeps a narrow bit-packed copy of (LEB128 / PLAIN integers)
   const u8* base;
 };
 

@@ -198,10 +198,35 @@ Status query_prepare(evql_query* q) {
       repacked = true;
     }
   }
-  for (auto& c : q->kp.cols) {
+  for (size_t i = 0; i < q->kp.cols.size(); ++i) {
     if (q->nested) break;
+    ColAccess& c = q->kp.cols[i];
     const ColumnLayout& cl = t->layout.columns[c.layout_index];
-    if (c.mode == ColAccess::BITPACKED) {
+    if (c.mode == ColAccess::PLAIN64 && cl.storage_type == ColumnEncoding::UINT64_PLAIN &&
+        cl.dlevel_max == 0 && (c.stype != EVQL_T_FLOAT64 || c.from_uint_to_float) &&
+        t->layout.num_rows >= t->narrow_min_rows) {
+      // A required UINT64_PLAIN column of a table that stays resident: kept once more as
+      // bit-packed pages of 8 / 16 / 32 bits where its maximum fits, like a LEB128 column
+      // (DESIGN.md 3.3).  The maximum comes from the cached statistics pass; the copy is
+      // made by the first operator that references the column.
+      auto hit = t->materialized.find(c.name);
+      if (hit == t->materialized.end()) {
+        double mx = 0;
+        Status st = column_abs_max(q, i, &mx);
+        if (!st.ok()) return st;
+        if (mx <= 4294967295.0) {
+          st = narrow_plain_column(t, c.layout_index, uint64_t(mx));
+          if (!st.ok()) return st;
+          hit = t->materialized.find(c.name);
+        }
+      }
+      if (hit != t->materialized.end() && hit->second.packed_bits) {
+        c.mode = ColAccess::BITPACKED;
+        c.bits = hit->second.packed_bits;
+        c.packed = true;
+        repacked = true;
+      }
+    } else if (c.mode == ColAccess::BITPACKED) {
       Status st = stream_bits(t, cl.data_pages, &c.bits);
       if (!st.ok()) return st;
     } else if (c.mode == ColAccess::SOA) {

@@ -131,7 +131,8 @@ struct DevBuf {
 struct MaterializedColumn {
   uint64_t* d_values = nullptr;
   uint8_t* d_tags = nullptr;
-  // UINT64_LEB128 re-encoded as bit-packed pages of width 8 / 16 / 32 (the narrowest
+  // a required UINT64_LEB128 or UINT64_PLAIN column (table.cc materialize_column /
+  // narrow_plain_column) kept as bit-packed pages of width 8 / 16 / 32 (the narrowest
   // that holds the column's maximum; widths that divide 32 decode with one shift):
   // the fused kernel then reads 1 - 4 bytes per value instead of an 8-byte SoA word
   uint8_t* d_packed = nullptr;
@@ -201,6 +202,8 @@ struct evql_table {
   // maximum |value| per column ("name#f" float view, "name#u" integer view): bounds of
   // exact float sums (EVQL_FLOAT_SUM_EXACT)
   std::map<std::string, double> col_absmax;
+  // required UINT64_PLAIN columns are kept narrow from this many rows on (~0 = never)
+  uint64_t narrow_min_rows;
   // nested scans: column flattened to one value per output row of the scans whose
   // deepest repeated column is `leaf` -- key (column, leaf) layout indices.  Like
   // `materialized`, decoded once per table and shared by every operator.
@@ -225,6 +228,7 @@ struct evql_table {
     evql::DevBuf<uint64_t> rec_offsets;
   };
   std::map<int, LeafLevels> leaf_cache;
+  evql_table();
   ~evql_table();
 };
 
@@ -464,6 +468,11 @@ Status defined_value_source(evql_table* t, int li, uint64_t nvalues, uint64_t* d
                             DevBuf<uint64_t>* owned);
 Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<uint8_t>* d_packed,
                    DevBuf<uint64_t>* d_packed_pages, uint32_t* bits_out);
+// Required UINT64_PLAIN columns kept narrow: in tables of at least
+// kNarrowMinRows rows (EVQL_NARROW_PLAIN overrides, read when a table becomes resident)
+static const uint64_t kNarrowMinRows = 1ull << 26;
+uint64_t narrow_plain_min_rows();
+Status narrow_plain_column(evql_table* t, int li, uint64_t maxv);
 Status materialize_column(evql_table* t, const ColAccess& ca);
 
 // nested.cc: the scans of a nested query, run by query_prepare
@@ -481,6 +490,8 @@ Status apply_where_resets(evql_query* q, const LeafLevels* leaf);
 // value_bounds.cc
 Status choose_exact_sum_scales(evql_query* q);
 Status choose_tuple_widths(evql_query* q);
+// maximum |value| of scan column i as the kernel sees it (cached per table column)
+Status column_abs_max(evql_query* q, size_t i, double* out);
 
 // query_run.cc
 Status query_prepare(evql_query* q);

@@ -1,6 +1,7 @@
 // table.cc -- a table's residency in HBM: the image and its page tables, and the decoded
 // ("materialised") forms of columns the fused kernel cannot read in place.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include "runtime.h"
 
@@ -109,6 +110,8 @@ Status table_from_image(evql_ctx* ctx, const void* image, size_t len, bool keep_
 
 }  // namespace evql
 
+evql_table::evql_table() : narrow_min_rows(evql::narrow_plain_min_rows()) {}
+
 evql_table::~evql_table() {
   if (d_image) hipFree(d_image);
   for (auto& v : d_pages) {
@@ -216,6 +219,31 @@ static uint64_t fixed_width_capacity(const ColumnLayout& c) {
   }
 }
 
+// the zeroed buffer and page table of `n` values as bit-packed pages of width `bits`
+// (`zero_all` = false: only the header and what lies behind the last block -- the caller
+// writes every block in full)
+static Status alloc_narrow_pages(hipStream_t s, uint64_t n, uint32_t bits, bool zero_all,
+                                 DevBuf<uint8_t>* d_packed,
+                                 DevBuf<uint64_t>* d_packed_pages) {
+  const uint64_t nblocks = (n + 127) / 128;
+  const uint64_t page_bytes = 16ull * bits * kBitpackBlocksPerPage;
+  const uint64_t npages = (nblocks + kBitpackBlocksPerPage - 1) / kBitpackBlocksPerPage;
+  // a tile reads up to 8192 rows beyond the last one: zero slack like the image's
+  const uint64_t bytes = 4 + npages * page_bytes + (1 << 20);
+  HIP_TRY(d_packed->alloc(bytes));
+  const uint64_t written = zero_all ? 0 : 4 + nblocks * 16ull * bits;
+  HIP_TRY(hipMemsetAsync(d_packed->p + written, 0, bytes - written, s));
+  std::vector<uint64_t> offs;
+  for (uint64_t pi = 0; pi < npages; ++pi) offs.push_back(pi == 0 ? 0 : 4 + pi * page_bytes);
+  offs.push_back(offs.back());  // (one past the end stays in bounds)
+  HIP_TRY(d_packed_pages->alloc(offs.size() * 8));
+  HIP_TRY(hipMemcpyAsync(d_packed_pages->p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
+  const uint32_t hdr = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
+  HIP_TRY(hipMemcpyAsync(d_packed->p, &hdr, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (offs / hdr live until here)
+  return Status();
+}
+
 // `n` u64 values as bit-packed pages (libsimdcomp layout, 131,072 values per page) of the
 // narrowest of 8 / 16 / 32 bits that holds their maximum; *bits = 0 when it does not fit
 // 32 bits.  Widths dividing 32 never straddle a word: the decode is one shift and one mask.
@@ -232,23 +260,48 @@ Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<u
   HIP_TRY(hipStreamSynchronize(s));
   if (maxv > 0xffffffffull) return Status();
   const uint32_t bits = maxv <= 0xffu ? 8 : (maxv <= 0xffffu ? 16 : 32);
-  const uint64_t nblocks = (n + 127) / 128;
-  const uint64_t page_bytes = 16ull * bits * kBitpackBlocksPerPage;
-  const uint64_t npages = (nblocks + kBitpackBlocksPerPage - 1) / kBitpackBlocksPerPage;
-  // a tile reads up to 8192 rows beyond the last one: zero slack like the image's
-  const uint64_t bytes = 4 + npages * page_bytes + (1 << 20);
-  HIP_TRY(d_packed->alloc(bytes));
-  HIP_TRY(hipMemsetAsync(d_packed->p, 0, bytes, s));
-  std::vector<uint64_t> offs;
-  for (uint64_t pi = 0; pi < npages; ++pi) offs.push_back(pi == 0 ? 0 : 4 + pi * page_bytes);
-  offs.push_back(offs.back());  // (one past the end stays in bounds)
-  HIP_TRY(d_packed_pages->alloc(offs.size() * 8));
-  HIP_TRY(hipMemcpyAsync(d_packed_pages->p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
-  const uint32_t hdr = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-  HIP_TRY(hipMemcpyAsync(d_packed->p, &hdr, 4, hipMemcpyHostToDevice, s));
+  Status st = alloc_narrow_pages(s, n, bits, true, d_packed, d_packed_pages);
+  if (!st.ok()) return st;
   HIP_TRY(launch_wr_bitpack(d_packed->p, d_packed_pages->p, d_values, nullptr, n, bits, s));
   HIP_TRY(hipStreamSynchronize(s));
   *bits_out = bits;
+  return Status();
+}
+
+// EVQL_NARROW_PLAIN: 0 = PLAIN columns are never kept narrow, N = in tables of at least N rows
+uint64_t narrow_plain_min_rows() {
+  if (const char* e = getenv("EVQL_NARROW_PLAIN")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end != e) return v == 0 ? ~0ull : v;  // 0 = off
+  }
+  return kNarrowMinRows;
+}
+
+// Required UINT64_PLAIN column `li`, whose maximum is `maxv`, once more as bit-packed pages
+// of the narrowest of 8 / 16 / 32 bits -- t->materialized[name] with packed_bits set and no
+// 8-byte words, what a required LEB128 column leaves there.  The file's own pages stay
+// (download_image, the LSM paths and table_rt_column read them).  No entry when the
+// maximum does not fit 32 bits.
+Status narrow_plain_column(evql_table* t, int li, uint64_t maxv) {
+  static_assert(kPlain64PageValues == kPlainPageSize / 8, "k_narrow_plain64's source page size");
+  const ColumnLayout& c = t->layout.columns[li];
+  const uint64_t n = t->layout.num_rows;
+  if (t->materialized.count(c.name) || maxv > 0xffffffffull || n == 0) return Status();
+  if (n > uint64_t(c.data_pages.size()) * (kPlainPageSize / 8)) return Status();  // (short file)
+  hipStream_t s = t->ctx->stream;
+  const uint32_t bits = maxv <= 0xffu ? 8 : (maxv <= 0xffffu ? 16 : 32);
+  MaterializedColumn m;
+  DevBuf<uint8_t> d_packed;
+  DevBuf<uint64_t> d_packed_pages;
+  Status st = alloc_narrow_pages(s, n, bits, false, &d_packed, &d_packed_pages);
+  if (!st.ok()) return st;
+  HIP_TRY(launch_narrow_plain64(t->d_image, t->d_pages[li][0], d_packed.p, d_packed_pages.p, n, bits, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  m.d_packed = d_packed.release();
+  m.d_packed_pages = d_packed_pages.release();
+  m.packed_bits = bits;
+  t->materialized[c.name] = std::move(m);
   return Status();
 }
 

@@ -59,7 +59,7 @@ static double expr_abs_bound(const ExprPtr& e, const std::vector<double>& colmax
 }
 
 // maximum |value| of scan column i as the kernel sees it (cached per table column)
-static Status column_abs_max(evql_query* q, size_t i, double* out) {
+Status column_abs_max(evql_query* q, size_t i, double* out) {
   evql_table* t = q->table;
   hipStream_t s = q->ctx->stream;
   const ColAccess& c = q->kp.cols[i];

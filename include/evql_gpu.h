@@ -254,6 +254,11 @@ int evql_table_column_info(const evql_table_t* t, int idx,
 /* size / copy-out of the image as it sits in HBM (tests of the generator) */
 uint64_t evql_table_image_size(const evql_table_t* t);
 int evql_table_download_image(const evql_table_t* t, void* dst, uint64_t len);
+/* Bytes of HBM the table holds at this moment: the image with its page tables plus
+ * everything cached on it since -- decoded columns, the narrow copies of LEB128 and
+ * PLAIN integer columns, string dictionaries, flattened nested columns.  Grows as
+ * operators touch new columns; what a memory budget should count, not the file size. */
+uint64_t evql_table_device_bytes(const evql_table_t* t);
 
 /*
  * Synthetic table generated directly into HBM in cstable v0.2.0 page layout
@@ -537,7 +542,10 @@ typedef struct {
   uint64_t rows_scanned;
   uint64_t rows_passed;
   uint64_t num_groups;
-  uint64_t algorithmic_bytes; /* SURVEY 8d B_alg of the columns referenced */
+  /* SURVEY 8d B_alg of the columns referenced: per column the file's payload bytes, or
+   * the bytes of the narrow copy the kernel streams instead (LEB128 / PLAIN integer
+   * columns kept as 8 / 16 / 32-bit pages) where that is less; + result bytes */
+  uint64_t algorithmic_bytes;
   double kernel_ms;           /* device time of the dominant (scan) kernel */
   double total_ms;            /* all kernels of the query                   */
   uint32_t n_kernel_launches;
