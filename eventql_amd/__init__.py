@@ -57,6 +57,7 @@ def lib():
     L.evql_ctx_synchronize.argtypes = [C.c_void_p]
     L.evql_ctx_stream.restype = C.c_void_p
     L.evql_ctx_stream.argtypes = [C.c_void_p]
+    L.evql_ctx_kernel_cache_stats.argtypes = [C.c_void_p, C.POINTER(K.KernelCacheStats)]
     L.evql_table_open_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
     L.evql_table_open_image.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.evql_table_close.argtypes = [C.c_void_p]
@@ -265,6 +266,12 @@ class Context:
     @property
     def stream(self):
         return lib().evql_ctx_stream(self.h)
+
+    def kernel_cache_stats(self):
+        """evql_ctx_kernel_cache_stats: capi.KernelCacheStats of this context"""
+        st = K.KernelCacheStats()
+        _check(lib().evql_ctx_kernel_cache_stats(self.h, C.byref(st)))
+        return st
 
     def open_file(self, path):
         t = C.c_void_p()
@@ -594,6 +601,13 @@ def compile_only(plan, columns, cache_dir=None):
     cd = (cache_dir or KERNEL_CACHE_DIR).encode()
     _check(lib().evql_compile_only(C.byref(plan.desc), infos, len(columns), cd, C.byref(size)))
     return size.value
+
+
+def kernel_cache_stats():
+    """the process-wide counters of the kernel cache (compile_only; no device needed)"""
+    st = K.KernelCacheStats()
+    _check(lib().evql_ctx_kernel_cache_stats(None, C.byref(st)))
+    return st
 
 
 class Hub:

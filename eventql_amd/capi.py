@@ -164,6 +164,15 @@ class QueryStats(C.Structure):
     ]
 
 
+class KernelCacheStats(C.Structure):
+    _fields_ = [
+        ("memory_hits", C.c_uint64),
+        ("disk_hits", C.c_uint64),
+        ("compiles", C.c_uint64),
+        ("compile_ms", C.c_double),
+    ]
+
+
 class PartialView(C.Structure):
     _fields_ = [
         ("device_words", C.c_void_p),

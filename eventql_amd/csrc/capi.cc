@@ -108,6 +108,18 @@ int evql_ctx_synchronize(evql_ctx_t* ctx) {
 
 void* evql_ctx_stream(evql_ctx_t* ctx) { return ctx->stream; }
 
+int evql_ctx_kernel_cache_stats(const evql_ctx_t* ctx, evql_kernel_cache_stats_t* out) {
+  API_TRY
+  if (!out) return fail(EVQL_EARG, "null argument");
+  const KernelCacheStats k = ctx ? ctx->kstats : process_kernel_cache_stats();
+  out->memory_hits = k.memory_hits;
+  out->disk_hits = k.disk_hits;
+  out->compiles = k.compiles;
+  out->compile_ms = k.compile_ms;
+  return EVQL_OK;
+  API_CATCH
+}
+
 // ---- tables -------------------------------------------------------------------------
 int evql_table_open_image(evql_ctx_t* ctx, const void* image, size_t len, evql_table_t** out) {
   API_TRY
@@ -973,7 +985,7 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
   for (auto& c : q.kp.cols) {
     if (c.mode == ColAccess::BITPACKED) c.bits = uint32_t(columns[c.layout_index].payload_bytes);
   }
-  q.source = generate_kernel_source(q.kp);
+  q.source = generate_kernel_source(&q.kp);
   std::vector<char> code;
   st = compile_to_code_object(q.source, &code, true);
   if (!st.ok()) return ret(st);

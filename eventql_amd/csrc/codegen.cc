@@ -56,6 +56,66 @@ struct Emitter {
   std::vector<std::string> string_literals;
   // index of this emitter's first literal among the translation unit's `evql_slit<i>`
   size_t lit_base = 0;
+  // the plan's numeric literal pool (KernelPlan::lit_pool), one per translation unit and
+  // shared by its row functions: slot i is read as A.lit[i]
+  std::vector<uint64_t>* pool = nullptr;
+
+  // the plan's scan columns (how each is read bounds its values)
+  const std::vector<ColAccess>* cols = nullptr;
+
+  static bool poolable(const ExprPtr& e) {
+    return e->kind == Expr::LITERAL && !e->lit_tag &&
+           (e->type == EVQL_T_UINT64 || e->type == EVQL_T_INT64 || e->type == EVQL_T_FLOAT64 ||
+            e->type == EVQL_T_TIMESTAMP64);
+  }
+  // an unsigned column whose values are read from 32 bits or fewer
+  bool narrow_input(const ExprPtr& e) const {
+    if (!cols || e->kind != Expr::INPUT || e->input >= cols->size()) return false;
+    if (e->type != EVQL_T_UINT64 && e->type != EVQL_T_TIMESTAMP64) return false;
+    const ColAccess& c = (*cols)[e->input];
+    if (c.stype != e->type) return false;
+    return c.mode == ColAccess::PLAIN32 ||
+           (c.mode == ColAccess::BITPACKED && c.bits >= 1 && c.bits <= 32);
+  }
+  // Compare of a narrow unsigned column with a pooled literal.  With the constant in the
+  // text the compiler knew both operands to fit 32 bits and compared 32 bits; against an
+  // unknown 64-bit word it would widen every value of the tile to a register pair (config
+  // 3 over 16-bit pages: 98 -> 114 VGPRs).  So the text splits the literal itself: its
+  // high half is tested once per wave on the scalar unit, the lanes compare 32 bits.
+  bool narrow_compare(const ExprPtr& e, std::string* rhs) {
+    const int fam = e->family;
+    if (fam < EVQL_FAM_EQ || fam > EVQL_FAM_GTE || e->args.size() != 2) return false;
+    if (e->type_slot != EVQL_TS_UINT64 && e->type_slot != EVQL_TS_TIMESTAMP64) return false;
+    if (!pool || pool->size() >= size_t(kMaxLits)) return false;
+    int ci = -1;
+    if (narrow_input(e->args[0]) && poolable(e->args[1])) ci = 0;
+    if (narrow_input(e->args[1]) && poolable(e->args[0])) ci = 1;
+    if (ci < 0) return false;
+    const Val c = emit(e->args[ci]), l = emit(e->args[1 - ci]);
+    // the relation as seen from the column: c OP l
+    const char* opr = nullptr;
+    bool when_high = false;  // the result when the literal does not fit 32 bits
+    switch (fam) {
+      case EVQL_FAM_EQ: opr = "=="; break;
+      case EVQL_FAM_NEQ: opr = "!="; when_high = true; break;
+      case EVQL_FAM_LT: opr = ci == 0 ? "<" : ">"; when_high = ci == 0; break;
+      case EVQL_FAM_LTE: opr = ci == 0 ? "<=" : ">="; when_high = ci == 0; break;
+      case EVQL_FAM_GT: opr = ci == 0 ? ">" : "<"; when_high = ci != 0; break;
+      case EVQL_FAM_GTE: opr = ci == 0 ? ">=" : "<="; when_high = ci != 0; break;
+      default: return false;
+    }
+    const std::string lo = "((u32) " + c.v + " " + opr + " (u32) " + l.v + ")";
+    const std::string hi = "((u32) (" + l.v + " >> 32) " + (when_high ? "!=" : "==") + " 0u)";
+    *rhs = "(" + hi + (when_high ? " | " : " & ") + lo + ")";
+    return true;
+  }
+
+  // the 64 bits of a numeric literal: a slot of the pool, or the constant itself
+  std::string lit_word(const ExprPtr& e, bool bake) {
+    if (bake || !pool || pool->size() >= size_t(kMaxLits)) return hex64(e->lit_bits);
+    pool->push_back(e->lit_bits);
+    return "A.lit[" + std::to_string(pool->size() - 1) + "]";
+  }
 
   std::string str_operand(const ExprPtr& x) {
     char b[96];
@@ -78,7 +138,8 @@ struct Emitter {
     }
   }
 
-  Val emit(const ExprPtr& e) {
+  // `bake`: a literal at `e` stays a constant of the text
+  Val emit(const ExprPtr& e, bool bake = false) {
     switch (e->kind) {
       case Expr::INPUT: {
         char v[16], g[16];
@@ -87,12 +148,22 @@ struct Emitter {
         return {v, g, e->type};
       }
       case Expr::LITERAL: {
+        // A numeric literal (UINT64, INT64, FLOAT64, TIMESTAMP64; not NULL) is data of the
+        // launch: the text reads its 64 bits from the kernel arguments (A.lit[i], a
+        // wave-uniform read at a constant index) and keeps only its type, so plans that
+        // differ in such values share one code object.  What stays in the text:
+        //   - BOOL literals and literals with a NULL tag: they decide control flow and tags;
+        //   - string literals (evql_slit<i>, str_operand);
+        //   - the right operand of div / mod / pow (`bake`): the compiler strength-reduces
+        //     a constant divisor and folds the zero-divisor check away;
+        //   - literals beyond the kMaxLits-th of a plan.
+        const std::string w = poolable(e) ? lit_word(e, bake) : hex64(e->lit_bits);
         std::string v;
         switch (e->type) {
-          case EVQL_T_FLOAT64: v = "evql_as_f64(" + hex64(e->lit_bits) + ")"; break;
-          case EVQL_T_INT64: v = "((i64) " + hex64(e->lit_bits) + ")"; break;
+          case EVQL_T_FLOAT64: v = "evql_as_f64(" + w + ")"; break;
+          case EVQL_T_INT64: v = "((i64) " + w + ")"; break;
           case EVQL_T_BOOL: v = e->lit_bits ? "true" : "false"; break;
-          default: v = hex64(e->lit_bits);
+          default: v = w;
         }
         return {v, e->lit_tag ? "1u" : "0u", e->type};
       }
@@ -141,8 +212,17 @@ struct Emitter {
       o << ind << "const " << ctype(e->type) << " " << t << " = " << rhs << ";\n";
       return {t, "0u", e->type};
     }
+    {
+      std::string narrow;
+      if (narrow_compare(e, &narrow)) {
+        std::string t = fresh("t");
+        o << ind << "const bool " << t << " = " << narrow << ";\n";
+        return {t, "0u", e->type};
+      }
+    }
     std::vector<Val> a;
-    for (const auto& x : e->args) a.push_back(emit(x));
+    const bool const_rhs = fam == EVQL_FAM_DIV || fam == EVQL_FAM_MOD || fam == EVQL_FAM_POW;
+    for (size_t i = 0; i < e->args.size(); ++i) a.push_back(emit(e->args[i], const_rhs && i == 1));
     std::string t = fresh("t");
     std::string rhs;
     auto bin = [&](const char* opr) { return "(" + a[0].v + " " + opr + " " + a[1].v + ")"; };

@@ -51,6 +51,9 @@ static const int kMaxExactSums = 4;
 
 static const int kMaxDistinct = 4;
 
+// slots of the numeric literal pool in the kernel arguments (EvqlArgs::lit, EVQL_MAX_LITS)
+static const int kMaxLits = 32;
+
 enum KeyMode {
   KEY_NONE = 0,    // no GROUP BY: one global group, register accumulators
   KEY_EXACT = 1,   // one fixed-width key: identity = value bits (+ NULL slot)
@@ -105,6 +108,11 @@ struct KernelPlan {
   bool bare_scan = false;
   std::vector<ExprPtr> scan_out;
   std::vector<bool> scan_out_nullable;  // may the value carry STAG_NULL?
+  // The 64-bit values of the plan's pooled numeric literals, in the order the generator met
+  // them (codegen.cc, case Expr::LITERAL): the text reads slot i as A.lit[i], every launch
+  // passes the values (fill_host_args).  Filled by generate_kernel_source; NOT part of the
+  // text, so plans that differ only here share one code object.
+  std::vector<uint64_t> lit_pool;
   int tile_rows() const { return block * 2 * unroll; }
 };
 
@@ -114,8 +122,8 @@ uint64_t lds_table_max_slots(const KernelPlan& kp);
 extern const uint64_t kPartitionAboveSlots;  // partitioned path for hint > this * LDS slots
 bool partitioned_path_possible(const KernelPlan& kp);
 
-// the generated translation unit (device library excluded)
-std::string generate_kernel_source(const KernelPlan& kp);
+// the generated translation unit (device library excluded); fills kp->lit_pool
+std::string generate_kernel_source(KernelPlan* kp);
 // 32-bit words of one partition tuple (identity, [identity 2], [row], update words)
 int partition_tuple_u32_words(const KernelPlan& kp);
 

@@ -169,6 +169,8 @@ struct Gen {
     s.str("");
     Emitter em;
     em.lit_base = lit_base;
+    em.pool = &pool;
+    em.cols = &kp.cols;
     body(em);
     const std::string fn = s.str();
     s.str("");
@@ -186,6 +188,8 @@ struct Gen {
   }
 
   size_t n_literals = 0;  // of evql_eval_row
+  // numeric literals are numbered once per plan, across its row functions (A.lit[i])
+  std::vector<uint64_t> pool;
   void eval_row() {
     n_literals = row_function(0, [&](Emitter& em) { eval_row_body(em); });
   }
@@ -1315,16 +1319,17 @@ struct Gen {
 
 int partition_tuple_u32_words(const KernelPlan& kp) { return Gen(kp).tuple_u32; }
 
-std::string generate_kernel_source(const KernelPlan& kp) {
-  Gen g(kp);
+std::string generate_kernel_source(KernelPlan* kp) {
+  Gen g(*kp);
   g.prologue();
   g.eval_row();
-  if (kp.bare_scan) {
+  if (kp->bare_scan) {
     g.bare_scan_kernels();
   } else {
     g.scan_kernel();
-    if (kp.partitioned) g.partition_kernels();
+    if (kp->partitioned) g.partition_kernels();
   }
-  if (kp.where_rows_kernel) g.where_rows_kernel();
+  if (kp->where_rows_kernel) g.where_rows_kernel();
+  kp->lit_pool = g.pool;
   return g.s.str();
 }

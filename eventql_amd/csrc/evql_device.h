@@ -25,6 +25,7 @@ typedef unsigned char u8;
 
 #define EVQL_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define EVQL_MAX_COLS 16
+#define EVQL_MAX_LITS 32
 #define EVQL_WAVE 64
 
 // status bits written by kernels, read by the host after the launch
@@ -68,7 +69,12 @@ struct EvqlArgs {
   // of |argument|
   double fscale[4];
   double fbound[4];
+  // The plan's numeric literals (KernelPlan::lit_pool): the generated text reads slot i as
+  // A.lit[i] with a constant i -- a wave-uniform read of the kernel-argument segment -- so
+  // a code object serves every query of its shape, whatever the values.
+  u64 lit[EVQL_MAX_LITS];
 };
+static_assert(sizeof(EvqlArgs) == 1240, "host mirror: HostArgs (runtime.h)");
 
 #define EVQL_ST_SUM_RANGE 32u
 // the multiple of the quantum nearest to x, split into a signed high part and 31 low

@@ -4,9 +4,11 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <mutex>
 #include "runtime.h"
 #include "sha1.h"
 
@@ -62,7 +64,34 @@ static bool plausible_code_object(const std::vector<char>& c) {
   return shoff <= c.size() && uint64_t(shentsize) * shnum <= c.size() - shoff;
 }
 
-Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache) {
+// process-wide counters: compilations outside any context (evql_compile_only)
+static std::mutex g_stats_mutex;
+static KernelCacheStats g_stats;
+
+KernelCacheStats process_kernel_cache_stats() {
+  std::lock_guard<std::mutex> lock(g_stats_mutex);
+  return g_stats;
+}
+
+namespace {
+// bumps `stats`, or the process-wide counters under their lock
+struct StatsRef {
+  KernelCacheStats* stats;
+  template <typename F>
+  void bump(F f) {
+    if (stats) {
+      f(*stats);
+    } else {
+      std::lock_guard<std::mutex> lock(g_stats_mutex);
+      f(g_stats);
+    }
+  }
+};
+}  // namespace
+
+Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache,
+                              KernelCacheStats* stats) {
+  StatsRef sr{stats};
   const std::string full = std::string(device_library_source()) + "\n" + source;
   std::string key = hex_digest(full);
   std::string cache_file;
@@ -72,10 +101,14 @@ Status compile_to_code_object(const std::string& source, std::vector<char>* code
     std::ifstream f(cache_file, std::ios::binary);
     if (f && use_cache) {
       code->assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-      if (plausible_code_object(*code)) return Status();
+      if (plausible_code_object(*code)) {
+        sr.bump([](KernelCacheStats& k) { k.disk_hits += 1; });
+        return Status();
+      }
       code->clear();
     }
   }
+  const auto t0 = std::chrono::steady_clock::now();
   hiprtcProgram prog;
   if (hiprtcCreateProgram(&prog, full.c_str(), "evql_fused.hip", 0, nullptr, nullptr) !=
       HIPRTC_SUCCESS) {
@@ -96,6 +129,12 @@ Status compile_to_code_object(const std::string& source, std::vector<char>* code
   code->resize(cs);
   hiprtcGetCode(prog, code->data());
   hiprtcDestroyProgram(&prog);
+  const double ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  sr.bump([ms](KernelCacheStats& k) {
+    k.compiles += 1;
+    k.compile_ms += ms;
+  });
   if (!cache_file.empty()) {
     mkdir(dir.c_str(), 0755);
     // (several processes -- one per GPU -- compile the same plan at the same time: each
@@ -117,18 +156,20 @@ Status compile_kernel(evql_ctx* ctx, const std::string& source, Module* out, boo
     auto it = ctx->modules.find(key);
     if (it != ctx->modules.end()) {
       *out = it->second;
+      ctx->kstats.memory_hits += 1;
       return Status();
     }
   }
+  KernelCacheStats* stats = ctx ? &ctx->kstats : nullptr;
   std::vector<char> code;
-  Status st = compile_to_code_object(source, &code, true);
+  Status st = compile_to_code_object(source, &code, true, stats);
   if (!st.ok()) return st;
   out->code_size = code.size();
   if (load_module) {
     if (hipModuleLoadData(&out->mod, code.data()) != hipSuccess) {
       // a damaged cache file: compile again (and replace it)
       (void) hipGetLastError();
-      st = compile_to_code_object(source, &code, false);
+      st = compile_to_code_object(source, &code, false, stats);
       if (!st.ok()) return st;
       out->code_size = code.size();
       HIP_TRY(hipModuleLoadData(&out->mod, code.data()));

@@ -100,7 +100,7 @@ static Status compile_plan_kernels(evql_query* q) {
     q->kp.part_fused = q->kp.part_bits > 8 && !q->part_fused_off &&
                        (end - begin) * tw * 8 <= (16ull << 30);
   }
-  q->source = generate_kernel_source(q->kp);
+  q->source = generate_kernel_source(&q->kp);
   Status st = compile_kernel(ctx, q->source, &q->module, true);
   if (!st.ok()) return st;
   // A plan with many columns / state words can outgrow the 128 VGPRs a 1024-thread
@@ -122,7 +122,7 @@ static Status compile_plan_kernels(evql_query* q) {
     }
     if (scratch == 0) break;
     q->kp.unroll /= 2;
-    q->source = generate_kernel_source(q->kp);
+    q->source = generate_kernel_source(&q->kp);
     st = compile_kernel(ctx, q->source, &q->module, true);
     if (!st.ok()) return st;
   }
@@ -405,6 +405,7 @@ void fill_host_args(evql_query* q, HostArgs* ap) {
     a.fscale[k] = std::ldexp(1.0, -q->fsum_exp[k]);
     a.fbound[k] = q->fsum_bound[k];
   }
+  for (size_t i = 0; i < kp.lit_pool.size() && i < size_t(kMaxLits); ++i) a.lit[i] = kp.lit_pool[i];
   for (size_t i = 0; i < kp.cols.size(); ++i) {
     const ColAccess& c = kp.cols[i];
     a.col[i].base = t->d_image;

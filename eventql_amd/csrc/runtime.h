@@ -38,6 +38,7 @@ struct HostArgs {
   uint64_t pairset_cap[4];
   double fscale[4];
   double fbound[4];
+  uint64_t lit[kMaxLits];  // KernelPlan::lit_pool
 };
 
 struct Status {
@@ -81,6 +82,17 @@ struct HostArgsWithPart {
   HostArgs a;
   HostPartArgs p;
 };
+// 984 bytes of pointers and bounds + the 256 bytes of the literal pool; with the largest
+// trailing struct a launch stays far below the 4 KiB kernel-argument segment
+static_assert(sizeof(HostArgs) == 1240, "device side: EvqlArgs (evql_device.h)");
+static_assert(sizeof(HostArgsWithPart) == 1320 && sizeof(HostArgsWithPart) <= 4096,
+              "kernel-argument segment");
+
+// what the kernel cache did (evql_ctx_kernel_cache_stats)
+struct KernelCacheStats {
+  uint64_t memory_hits = 0, disk_hits = 0, compiles = 0;
+  double compile_ms = 0;
+};
 
 }  // namespace evql
 
@@ -90,6 +102,7 @@ struct evql_ctx {
   bool own_stream = false;
   int num_cus = 256;
   std::map<std::string, evql::Module> modules;  // by source fingerprint
+  evql::KernelCacheStats kstats;
 };
 
 namespace evql {
@@ -438,7 +451,10 @@ int fail(int code, const std::string& m);
 
 // kernel_cache.cc
 void set_cache_dir(const std::string& d);
-Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache);
+// `stats`: the counters to bump; NULL = the process-wide ones (evql_compile_only)
+Status compile_to_code_object(const std::string& source, std::vector<char>* code, bool use_cache,
+                              KernelCacheStats* stats = nullptr);
+KernelCacheStats process_kernel_cache_stats();
 Status compile_kernel(evql_ctx* ctx, const std::string& source, Module* out,
                       bool load_module);
 Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan,

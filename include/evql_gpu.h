@@ -219,6 +219,14 @@ void evql_ctx_destroy(evql_ctx_t* ctx);
 int evql_ctx_synchronize(evql_ctx_t* ctx);
 void* evql_ctx_stream(evql_ctx_t* ctx);
 
+/* What the kernel cache did for this context: plan kernels found among the modules the
+ * context holds (memory_hits), read from the on-disk cache (disk_hits), compiled with
+ * hiprtc (compiles, and the wall time they took).  A query whose create leaves `compiles`
+ * unchanged ran without a compile.  ctx == NULL: the process-wide counters of
+ * evql_compile_only, which need no device. */
+typedef struct { uint64_t memory_hits, disk_hits, compiles; double compile_ms; } evql_kernel_cache_stats_t;
+int evql_ctx_kernel_cache_stats(const evql_ctx_t* ctx, evql_kernel_cache_stats_t* out);
+
 /* ------------------------------------------------------------------------ */
 /* tables: a cstable v0.2.0 file resident in HBM                              */
 /* ------------------------------------------------------------------------ */
@@ -495,6 +503,12 @@ typedef struct {
 #define EVQL_FLOAT_SUM_EXACT 1
 
 /* Lowers the plan to a fused kernel and compiles it (cached by fingerprint).
+ * The fingerprint covers the plan's SHAPE: everything but the values of its pooled
+ * numeric literals -- UINT64 / INT64 / FLOAT64 / TIMESTAMP64 literals that are not NULL,
+ * the first 32 of a plan, other than the right operand of div / mod / pow.  Those values
+ * travel with every launch, so `time > <now>` with a fresh <now> finds its kernel in
+ * the cache.  A literal that changes a decision of the planner (a WHERE that is always
+ * true, the width of a partition tuple member) changes the shape.
  * Replaces DefaultScheduler::buildGroupByExpression + buildSequentialScan
  * (sql/scheduler.cc:134-182).  EVQL_ENOTSUP => not lowerable. */
 int evql_query_create(evql_ctx_t* ctx, evql_table_t* table,
@@ -812,7 +826,8 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch,
 /* ------------------------------------------------------------------------ */
 /* Compile the fused kernel of `plan` for gfx950 without a device (used by
  * __graft_entry__.build() and the CPU test-suite).  Stores the code object in
- * the on-disk kernel cache when cache_dir != NULL. */
+ * the on-disk kernel cache when cache_dir != NULL.  Plans of one shape (see
+ * evql_query_create) give one code object. */
 int evql_compile_only(const evql_plan_desc_t* plan,
                       const evql_column_info_t* columns, int ncolumns,
                       const char* cache_dir, size_t* code_size);
