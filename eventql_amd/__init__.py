@@ -69,6 +69,8 @@ def lib():
     L.evql_table_image_size.argtypes = [C.c_void_p]
     L.evql_table_device_bytes.restype = C.c_uint64
     L.evql_table_device_bytes.argtypes = [C.c_void_p]
+    L.evql_table_zone_map.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
     L.evql_table_download_image.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.evql_table_generate.argtypes = [C.c_void_p, C.POINTER(K.SynthSpec), C.POINTER(C.c_void_p)]
     L.evql_table_from_device_columns.argtypes = [C.c_void_p, C.POINTER(K.ColumnSpec), C.c_int,
@@ -113,6 +115,7 @@ def lib():
     L.evql_query_next_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(K.ColumnBuf),
                                         C.POINTER(C.c_size_t)]
     L.evql_query_stats.argtypes = [C.c_void_p, C.POINTER(K.QueryStats)]
+    L.evql_query_zone_stats.argtypes = [C.c_void_p, C.POINTER(K.ZoneStats)]
     L.evql_query_kernel_source.restype = C.c_char_p
     L.evql_query_kernel_source.argtypes = [C.c_void_p]
     L.evql_query_record_words.restype = C.c_uint32
@@ -363,6 +366,19 @@ class Table:
         narrow copies, dictionaries, flattened nested columns)"""
         return lib().evql_table_device_bytes(self.h)
 
+    def zone_map(self, name):
+        """evql_table_zone_map: (zmin, zmax) of every 2048 rows of column `name` as numpy
+        uint64 arrays; built on first use and cached on the table"""
+        import numpy as np
+        n = C.c_size_t()
+        _check(lib().evql_table_zone_map(self.h, name.encode(), None, None, 0, C.byref(n)))
+        zmin = np.zeros(n.value, dtype=np.uint64)
+        zmax = np.zeros(n.value, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        _check(lib().evql_table_zone_map(self.h, name.encode(), zmin.ctypes.data_as(u64p),
+                                         zmax.ctypes.data_as(u64p), n.value, C.byref(n)))
+        return zmin, zmax
+
     def query(self, plan):
         q = C.c_void_p()
         _check(lib().evql_query_create(self.ctx.h, self.h, C.byref(plan.desc), C.byref(q)))
@@ -451,6 +467,12 @@ class Query:
         s = K.QueryStats()
         _check(lib().evql_query_stats(self.h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in K.QueryStats._fields_}
+
+    def zone_stats(self):
+        """evql_query_zone_stats: what zone maps pruned in the last execute"""
+        s = K.ZoneStats()
+        _check(lib().evql_query_zone_stats(self.h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in K.ZoneStats._fields_}
 
     def kernel_source(self):
         return lib().evql_query_kernel_source(self.h).decode()

@@ -164,6 +164,19 @@ class QueryStats(C.Structure):
     ]
 
 
+class ZoneStats(C.Structure):
+    """evql_zone_stats_t"""
+    _fields_ = [
+        ("conjuncts_used", C.c_uint32),
+        ("zone_rows", C.c_uint32),
+        ("zones_total", C.c_uint64),
+        ("zones_excluded", C.c_uint64),
+        ("tile_rows", C.c_uint64),
+        ("tiles_total", C.c_uint64),
+        ("tiles_skipped", C.c_uint64),
+    ]
+
+
 class KernelCacheStats(C.Structure):
     _fields_ = [
         ("memory_hits", C.c_uint64),

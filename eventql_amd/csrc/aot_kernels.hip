@@ -1008,6 +1008,112 @@ __global__ void __launch_bounds__(kBlock) k_max_u64(const u64* values, u64 n, u6
   if ((threadIdx.x & 63) == 0 && m) atomicMax((unsigned long long*) out, (unsigned long long) m);
 }
 
+// ---- zone maps (aot_kernels.h) ---------------------------------------------------------
+__device__ __forceinline__ void zone_take(u64 v, u64& lo, u64& hi) {
+  lo = v < lo ? v : lo;
+  hi = v > hi ? v : hi;
+}
+
+__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int d) {
+  const u32 lo = __shfl_xor((u32) v, d, 64), hi = __shfl_xor((u32) (v >> 32), d, 64);
+  return (u64) lo | ((u64) hi << 32);
+}
+
+// one workgroup per zone of kZoneRowsDev rows, 8 values per thread
+constexpr u64 kZoneRowsDev = EVQL_ZONE_ROWS;
+static_assert(kZoneRowsDev == 8 * kBlock, "8 values per thread");
+
+__global__ void __launch_bounds__(kBlock) k_zone_minmax(const u8* image, RtColumn col, u64 n,
+                                                        u64* zmin, u64* zmax) {
+  const u32 tid = threadIdx.x;
+  const u64 base = (u64) blockIdx.x * kZoneRowsDev;
+  const u8* img = col.base ? col.base : image;
+  const u64* pages = (const u64*) col.pages;
+  u64 lo = ~0ull, hi = 0;
+  if (col.mode == 0) {  // PLAIN64: two values per 16-byte non-temporal load
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const u64 r = base + ((u64) (k * kBlock) + tid) * 2;
+      if (r + 1 < n) {
+        u64 a, b;
+        evql_plain64_x2(img, pages, r, a, b);
+        zone_take(a, lo, hi);
+        zone_take(b, lo, hi);
+      } else if (r < n) {
+        zone_take(evql_plain64(img, pages, r), lo, hi);
+      }
+    }
+  } else if (col.mode == 1) {  // PLAIN32: four values per 16-byte non-temporal load
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const u64 r = base + ((u64) (k * kBlock) + tid) * 4;
+      if (r + 3 < n) {
+        const u8* p = img + pages[r >> 17] + ((r & 0x1ffffull) << 2);
+        const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
+        zone_take(q.x, lo, hi);
+        zone_take(q.y, lo, hi);
+        zone_take(q.z, lo, hi);
+        zone_take(q.w, lo, hi);
+      } else {
+        for (u64 j = r; j < n && j < r + 4; ++j) zone_take(evql_plain32(img, pages, j), lo, hi);
+      }
+    }
+  } else {  // bit-packed pages (in place or a narrow copy), 8-byte SoA
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const u64 r = base + (u64) (k * kBlock) + tid;
+      if (r < n) zone_take(rt_column_value(image, col, r), lo, hi);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const u64 l2 = shfl_xor_u64(lo, d), h2 = shfl_xor_u64(hi, d);
+    lo = l2 < lo ? l2 : lo;
+    hi = h2 > hi ? h2 : hi;
+  }
+  __shared__ u64 wlo[kBlock / 64], whi[kBlock / 64];
+  if ((tid & 63u) == 0) {
+    wlo[tid >> 6] = lo;
+    whi[tid >> 6] = hi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) {
+      lo = wlo[w] < lo ? wlo[w] : lo;
+      hi = whi[w] > hi ? whi[w] : hi;
+    }
+    zmin[blockIdx.x] = lo;
+    zmax[blockIdx.x] = hi;
+  }
+}
+
+// one thread per bit of the bitmap; a wave's ballot is two of its words
+__global__ void __launch_bounds__(kBlock) k_zone_select(ZoneSelectArgs a) {
+  const u64 z = (u64) blockIdx.x * kBlock + threadIdx.x;
+  const bool in = z < a.n_zones;
+  bool ex = false;
+  if (in) {
+    for (u32 c = 0; c < a.n_conjuncts; ++c) {
+      const u64 mn = a.zmin[c][z], mx = a.zmax[c][z], l = a.lit[c];
+      bool e;
+      switch (a.op[c]) {
+        case ZONE_GT: e = mx <= l; break;
+        case ZONE_GTE: e = mx < l; break;
+        case ZONE_LT: e = mn >= l; break;
+        case ZONE_LTE: e = mn > l; break;
+        default: e = l < mn || l > mx;  // ZONE_EQ
+      }
+      ex = ex || e;
+    }
+  }
+  const u64 counted = __ballot(ex);
+  const u64 b = __ballot(ex || !in);  // (zones behind the table hold no row)
+  const u32 lane = threadIdx.x & 63u;
+  const u64 w = z >> 5;
+  if ((lane == 0 || lane == 32) && w < a.n_words) a.bits[w] = lane ? (u32) (b >> 32) : (u32) b;
+  if (lane == 0 && counted) atomicAdd((unsigned long long*) a.excluded, (unsigned long long) __popcll(counted));
+}
+
 // ---- STRING_PLAIN value boundaries (see aot_kernels.h) --------------------------------
 typedef unsigned short u16;
 
@@ -2342,6 +2448,22 @@ hipError_t launch_column_abs_max(const uint8_t* image, const RtColumn& col, uint
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_column_abs_max, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, image,
                      col, (u64) n, is_float, (u64*) out);
+  return hipGetLastError();
+}
+
+hipError_t launch_zone_minmax(const uint8_t* image, const RtColumn& col, uint64_t n, uint64_t* zmin,
+                              uint64_t* zmax, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint64_t zones = (n + kZoneRowsDev - 1) / kZoneRowsDev;
+  hipLaunchKernelGGL(k_zone_minmax, dim3((unsigned) zones), dim3(kBlock), 0, s, image, col, (u64) n,
+                     (u64*) zmin, (u64*) zmax);
+  return hipGetLastError();
+}
+
+hipError_t launch_zone_select(const ZoneSelectArgs& a, hipStream_t s) {
+  if (a.n_words == 0) return hipSuccess;
+  const uint64_t blocks = (a.n_words * 32 + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_zone_select, dim3((unsigned) blocks), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

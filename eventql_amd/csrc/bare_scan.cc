@@ -102,6 +102,7 @@ Status bare_launch(evql_query* q) {
   fill_host_args(q, &ac.a);
   const HostArgs& a = ac.a;
   b.ntiles = a.ntiles;
+  zone_stats_after_run(q, a.ntiles, 0);
   if (b.tiles_cap < b.ntiles + 1) {
     HIP_TRY(b.d_tile_count.alloc((b.ntiles + 1) * 4));
     HIP_TRY(b.d_tile_off.alloc((b.ntiles + 1) * 8));
@@ -147,8 +148,10 @@ Status bare_finish(evql_query* q) {
   hipStream_t s = q->ctx->stream;
   uint32_t status[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(status, q->d_status, 16, hipMemcpyDeviceToHost, s));
+  uint64_t skipped = 0;
   if (b.counted_on_device) {
     HIP_TRY(hipMemcpyAsync(b.tile_off.data(), b.d_tile_off, (b.ntiles + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&skipped, q->d_counters + 5, 8, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
   q->launched = false;
@@ -159,6 +162,7 @@ Status bare_finish(evql_query* q) {
   q->stats.kernel_ms = ms;
   q->stats.total_ms = ms;
   q->stats.rows_passed = b.tile_off.back();
+  q->zstats.tiles_skipped = skipped;
   if (q->reported_rows_scanned != ~0ull) q->stats.rows_scanned = q->reported_rows_scanned;
   q->stats.num_groups = 0;
   q->stats.used_lds_table = 0;

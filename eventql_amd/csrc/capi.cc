@@ -181,6 +181,8 @@ uint64_t evql_table_device_bytes(const evql_table_t* t) {
     add(m.d_packed);
     add(m.d_packed_pages);
   }
+  // (zone maps are not counted: 16 B per 2048 rows, and a plan with a range conjunct over a
+  // table without narrow copies leaves this figure where it was)
   for (const auto& kv : t->dicts) {
     add(kv.second.d_codes);
     add(kv.second.d_code_pages);
@@ -197,6 +199,26 @@ uint64_t evql_table_device_bytes(const evql_table_t* t) {
     add(kv.second.rec_offsets.p);
   }
   return total;
+}
+
+int evql_table_zone_map(evql_table_t* t, const char* column, uint64_t* zmin, uint64_t* zmax,
+                        size_t cap, size_t* n) {
+  API_TRY
+  if (!t || !column || !n) return fail(EVQL_EARG, "null argument");
+  if (hipSetDevice(t->ctx->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  const evql_table::ZoneMap* zm = nullptr;
+  Status st = table_zone_map(t, column, &zm);
+  if (!st.ok()) return ret(st);
+  *n = size_t(zm->n_zones);
+  const size_t k = std::min<size_t>(cap, size_t(zm->n_zones));
+  if (k && zmin && hipMemcpy(zmin, zm->zmin, k * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    return fail(EVQL_EDEVICE, "download failed");
+  }
+  if (k && zmax && hipMemcpy(zmax, zm->zmax, k * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    return fail(EVQL_EDEVICE, "download failed");
+  }
+  return EVQL_OK;
+  API_CATCH
 }
 
 int evql_table_download_image(const evql_table_t* t, void* dst, uint64_t len) {
@@ -784,6 +806,19 @@ int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out) {
   }
   bytes += q->stats.num_groups * 8 * (1 + q->kp.aggs.size());
   out->algorithmic_bytes = bytes;
+  return EVQL_OK;
+}
+
+int evql_query_zone_stats(const evql_query_t* q, evql_zone_stats_t* out) {
+  if (!q || !out) return fail(EVQL_EARG, "null argument");
+  *out = q->zstats;
+  out->zone_rows = uint32_t(kZoneRows);
+  for (const evql_query* part : q->chain) {  // a chain: the sums over its files
+    out->zones_total += part->zstats.zones_total;
+    out->zones_excluded += part->zstats.zones_excluded;
+    out->tiles_total += part->zstats.tiles_total;
+    out->tiles_skipped += part->zstats.tiles_skipped;
+  }
   return EVQL_OK;
 }
 

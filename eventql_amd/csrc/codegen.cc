@@ -35,6 +35,17 @@ const char* op_name(int op) {
   return n[op];
 }
 
+// An integer div / mod gets a zero-divisor check unless its divisor is a non-zero integer
+// literal (which stays a constant of the text, Emitter::emit `bake`).
+bool needs_zero_check(const ExprPtr& e) {
+  if (e->kind != Expr::CALL || (e->family != EVQL_FAM_DIV && e->family != EVQL_FAM_MOD)) return false;
+  if (e->type_slot == EVQL_TS_FLOAT64 || e->args.size() != 2) return false;
+  const ExprPtr& d = e->args[1];
+  const bool int_lit = d->kind == Expr::LITERAL && !d->lit_tag &&
+                       (d->type == EVQL_T_UINT64 || d->type == EVQL_T_INT64 || d->type == EVQL_T_TIMESTAMP64);
+  return !(int_lit && d->lit_bits != 0);
+}
+
 struct Val {
   std::string v;  // payload expression (already typed)
   std::string g;  // tag expression (u32)
@@ -252,8 +263,12 @@ struct Emitter {
           // integer division by zero raises in the reference (math.cc:136-164):
           // flag it and keep going with 0; the host turns the flag into ERUNTIME
           o << ind << ctype(e->type) << " " << t << " = 0;\n";
-          o << ind << "if (" << a[1].v << " == 0) { atomicOr(&A.status[0], "
-            << (is_div ? "EVQL_ST_DIV_BY_ZERO" : "EVQL_ST_MOD_BY_ZERO") << "); } else {\n";
+          if (needs_zero_check(e)) {
+            o << ind << "if (" << a[1].v << " == 0) { atomicOr(&A.status[0], "
+              << (is_div ? "EVQL_ST_DIV_BY_ZERO" : "EVQL_ST_MOD_BY_ZERO") << "); } else {\n";
+          } else {
+            o << ind << "{\n";
+          }
           if (ts == EVQL_TS_INT64) {
             if (is_div) {
               o << ind << "  " << t << " = (" << a[0].v
@@ -298,6 +313,15 @@ struct Emitter {
 };
 
 }  // namespace
+
+bool expr_prints_zero_check(const ExprPtr& e) {
+  if (!e) return false;
+  if (needs_zero_check(e)) return true;
+  for (const auto& a : e->args) {
+    if (expr_prints_zero_check(a)) return true;
+  }
+  return false;
+}
 
 // kernel skeletons (scan, partition count / scatter / aggregate)
 #include "codegen_kernels.inc"

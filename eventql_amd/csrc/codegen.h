@@ -54,6 +54,19 @@ static const int kMaxDistinct = 4;
 // slots of the numeric literal pool in the kernel arguments (EvqlArgs::lit, EVQL_MAX_LITS)
 static const int kMaxLits = 32;
 
+// Zone maps: rows per zone, aligned to row 0.  A kernel tile is
+// block * 2 * unroll rows (block 256 or 1024, unroll a power of two): a whole number of
+// zones, or a divisor of one.
+static const uint64_t kZoneRows = 2048;
+static const int kMaxZoneConjuncts = 4;
+
+// a top-level conjunct `column <op> literal` of WHERE that can exclude zones
+struct ZoneConjunct {
+  int col = -1;       // scan column (index into KernelPlan::cols)
+  uint32_t op = 0;    // ZoneOp (aot_kernels.h), as seen from the column side
+  uint64_t lit = 0;   // the literal; data of k_zone_select, never part of the kernel text
+};
+
 enum KeyMode {
   KEY_NONE = 0,    // no GROUP BY: one global group, register accumulators
   KEY_EXACT = 1,   // one fixed-width key: identity = value bits (+ NULL slot)
@@ -113,6 +126,10 @@ struct KernelPlan {
   // passes the values (fill_host_args).  Filled by generate_kernel_source; NOT part of the
   // text, so plans that differ only here share one code object.
   std::vector<uint64_t> lit_pool;
+  // The conjuncts of WHERE that prune zones (planner.cc zone_conjuncts_of).  Non-empty: the
+  // tile loops test EvqlArgs::tile_skip.  Whether a conjunct is listed depends on the plan's
+  // shape only, never on the literal's value.
+  std::vector<ZoneConjunct> zone_conjuncts;
   int tile_rows() const { return block * 2 * unroll; }
 };
 
@@ -121,6 +138,10 @@ void choose_launch_shape(KernelPlan* kp, uint64_t hint);
 uint64_t lds_table_max_slots(const KernelPlan& kp);
 extern const uint64_t kPartitionAboveSlots;  // partitioned path for hint > this * LDS slots
 bool partitioned_path_possible(const KernelPlan& kp);
+
+// does evaluating `e` print a zero-divisor check anywhere (an integer div / mod whose divisor
+// is not a non-zero literal)?  Such an expression can raise; the emitter's own condition.
+bool expr_prints_zero_check(const ExprPtr& e);
 
 // the generated translation unit (device library excluded); fills kp->lit_pool
 std::string generate_kernel_source(KernelPlan* kp);

@@ -58,7 +58,11 @@ struct EvqlArgs {
   u64* gtab;       // HBM group table: word w of slot s at gtab[s*W + w]
   u64 gcap;        // slots (power of two); two extra special slots follow
   u32* status;     // [0] error bits, [1] reserved
-  u64* counters;   // [0] rows passed, [1] rows aggregated via LDS overflow
+  u64* counters;   // [0] rows passed, [1] rows aggregated via LDS overflow, [5] tiles skipped
+  // Zone maps: bit (z & 31) of word (z >> 5) set = no row of zone z (EVQL_ZONE_ROWS rows,
+  // aligned to row 0) can pass WHERE; zones behind the table's last are set too.  NULL =
+  // nothing is excluded.  Read only by kernels of plans with pruning conjuncts.
+  const u32* tile_skip;
   EvqlColArg col[EVQL_MAX_COLS];
   // count_distinct: one set of (group, value) pairs per aggregate, 3 word planes of
   // pairset_cap[i] (power of two) slots: group identity, value, second identity word
@@ -74,7 +78,19 @@ struct EvqlArgs {
   // a code object serves every query of its shape, whatever the values.
   u64 lit[EVQL_MAX_LITS];
 };
-static_assert(sizeof(EvqlArgs) == 1240, "host mirror: HostArgs (runtime.h)");
+static_assert(sizeof(EvqlArgs) == 1248, "host mirror: HostArgs (runtime.h)");
+
+#define EVQL_ZONE_ROWS 2048
+// Are the ZONES (a power of two <= 32) aligned zones that start at zone `zi` all excluded?
+// They lie in one word.  `zi` is uniform over the workgroup, so the word is read through
+// the constant address space: one scalar load, no per-lane load and no VGPR.
+template <u32 ZONES>
+__device__ __forceinline__ bool evql_zones_excluded(const u32* skip, u64 zi) {
+  typedef const u32 __attribute__((address_space(4))) * evql_cu32p;
+  const u32 w = ((evql_cu32p) (u64) skip)[zi >> 5];
+  const u32 mask = ZONES >= 32 ? 0xffffffffu : ((1u << ZONES) - 1u);
+  return ((w >> (u32) (zi & 31ull)) & mask) == mask;
+}
 
 #define EVQL_ST_SUM_RANGE 32u
 // the multiple of the quantum nearest to x, split into a signed high part and 31 low

@@ -151,6 +151,47 @@ bool expr_may_be_null(const ExprPtr& e, const std::vector<ColAccess>& cols) {
   }
 }
 
+// Zone maps: the conjuncts of the top-level AND tree of `e` that are `column <op> literal`
+// (eq / lt / lte / gt / gte of family type uint64 or timestamp64, either operand order)
+// over a bare reference of a qualifying column.  Anything under an OR, an IF, a negation or
+// a cast is not a conjunct of this form.  The literal's VALUE plays no part in the decision.
+void collect_zone_conjuncts(const ExprPtr& e, const TableLayout& layout,
+                            const std::vector<ColAccess>& cols, std::vector<ZoneConjunct>* out) {
+  if (!e || e->kind != Expr::CALL) return;
+  if (e->family == EVQL_FAM_LOGICAL_AND && e->args.size() == 2) {
+    collect_zone_conjuncts(e->args[0], layout, cols, out);
+    collect_zone_conjuncts(e->args[1], layout, cols, out);
+    return;
+  }
+  if (out->size() >= size_t(kMaxZoneConjuncts) || e->args.size() != 2) return;
+  if (e->type_slot != EVQL_TS_UINT64 && e->type_slot != EVQL_TS_TIMESTAMP64) return;
+  auto unsigned_type = [](uint32_t t) { return t == EVQL_T_UINT64 || t == EVQL_T_TIMESTAMP64; };
+  int ci = -1;
+  for (int k = 0; k < 2; ++k) {
+    const ExprPtr &c = e->args[k], &l = e->args[1 - k];
+    if (c->kind == Expr::INPUT && l->kind == Expr::LITERAL && !l->lit_tag && unsigned_type(l->type)) ci = k;
+  }
+  if (ci < 0) return;
+  const ExprPtr& c = e->args[ci];
+  if (c->input >= cols.size() || !unsigned_type(c->type)) return;
+  const ColAccess& ca = cols[c->input];
+  if (ca.stype != c->type || ca.layout_index < 0) return;
+  if (ca.from_uint_to_float || ca.bool_normalize || ca.string_hash || ca.has_tags) return;
+  if (!zone_column_qualifies(layout.columns[ca.layout_index])) return;
+  ZoneConjunct z;
+  z.col = int(c->input);
+  z.lit = e->args[1 - ci]->lit_bits;
+  switch (e->family) {  // as seen from the column side
+    case EVQL_FAM_EQ: z.op = ZONE_EQ; break;
+    case EVQL_FAM_LT: z.op = ci == 0 ? ZONE_LT : ZONE_GT; break;
+    case EVQL_FAM_LTE: z.op = ci == 0 ? ZONE_LTE : ZONE_GTE; break;
+    case EVQL_FAM_GT: z.op = ci == 0 ? ZONE_GT : ZONE_LT; break;
+    case EVQL_FAM_GTE: z.op = ci == 0 ? ZONE_GTE : ZONE_LTE; break;
+    default: return;
+  }
+  out->push_back(z);
+}
+
 int op_for_minmax(uint32_t fn) {
   switch (fn) {
     case EVQL_AGG_MIN_UINT64: return 2;
@@ -745,6 +786,15 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
     bool elsewhere = false;
     for (uint32_t u2 : used) elsewhere = elsewhere || u2 == ki;
     if (!elsewhere) q->dict_candidate = int(ki);
+  }
+
+  // Zone maps, flat scans only.  logical_and is eager in the reference: a
+  // WHERE that can raise does so on rows its other conjuncts reject, hence no pruning
+  // wherever the emitter prints a zero-divisor check.  EVQL_ZONE_MAPS=0 switches it off.
+  kp.zone_conjuncts.clear();
+  const char* zm = getenv("EVQL_ZONE_MAPS");
+  if (!nested && kp.where && !(zm && strcmp(zm, "0") == 0) && !expr_prints_zero_check(kp.where)) {
+    collect_zone_conjuncts(kp.where, layout, kp.cols, &kp.zone_conjuncts);
   }
 
   choose_launch_shape(&kp, plan->groups_hint);

@@ -241,6 +241,12 @@ Status query_prepare(evql_query* q) {
       }
     }
   }
+  {
+    // zone maps: statistics of the pruning columns (cached on the table), then the bitmap
+    // of the zones this query's literals exclude; every later execute reuses it
+    Status stz = query_zone_select(q);
+    if (!stz.ok()) return stz;
+  }
   if (q->dict_candidate >= 0 && !q->nested) {
     // a STRING key with a usable dictionary: the kernels group by its 32-bit codes.
     // (Here, behind the loop above: the record-level copy of the plan must know the
@@ -401,6 +407,7 @@ void fill_host_args(evql_query* q, HostArgs* ap) {
   a.gcap = q->gcap;
   a.status = q->d_status;
   a.counters = q->d_counters;
+  a.tile_skip = q->tile_skip;
   for (int k = 0; k < kp.n_exact; ++k) {
     a.fscale[k] = std::ldexp(1.0, -q->fsum_exp[k]);
     a.fbound[k] = q->fsum_bound[k];
@@ -475,6 +482,7 @@ Status query_launch(evql_query* q) {
 
   HostArgs a{};
   fill_host_args(q, &a);
+  zone_stats_after_run(q, a.ntiles, 0);
   if (kp.n_distinct > 0 && !q->keep_table) {
     // count_distinct pair sets: emptied before every launch
     if (q->pairset_cap == 0) {
@@ -727,6 +735,7 @@ Status query_finish(evql_query* q) {
     uint64_t counters[8];
     HIP_TRY(hipMemcpy(counters, q->d_counters, 64, hipMemcpyDeviceToHost));
     q->stats.rows_passed = counters[0];
+    q->zstats.tiles_skipped = counters[5];
     if (q->reported_rows_scanned != ~0ull) q->stats.rows_scanned = q->reported_rows_scanned;
     q->stats.used_lds_table = q->kp.lds_slots > 0;
     q->launched = false;

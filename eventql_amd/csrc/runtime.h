@@ -33,6 +33,7 @@ struct HostArgs {
   uint64_t gcap;
   uint32_t* status;
   uint64_t* counters;
+  const uint32_t* tile_skip;  // evql_query::tile_skip
   HostColArg col[16];
   uint64_t* pairset[4];
   uint64_t pairset_cap[4];
@@ -82,10 +83,10 @@ struct HostArgsWithPart {
   HostArgs a;
   HostPartArgs p;
 };
-// 984 bytes of pointers and bounds + the 256 bytes of the literal pool; with the largest
+// 992 bytes of pointers and bounds + the 256 bytes of the literal pool; with the largest
 // trailing struct a launch stays far below the 4 KiB kernel-argument segment
-static_assert(sizeof(HostArgs) == 1240, "device side: EvqlArgs (evql_device.h)");
-static_assert(sizeof(HostArgsWithPart) == 1320 && sizeof(HostArgsWithPart) <= 4096,
+static_assert(sizeof(HostArgs) == 1248, "device side: EvqlArgs (evql_device.h)");
+static_assert(sizeof(HostArgsWithPart) == 1328 && sizeof(HostArgsWithPart) <= 4096,
               "kernel-argument segment");
 
 // what the kernel cache did (evql_ctx_kernel_cache_stats)
@@ -215,6 +216,14 @@ struct evql_table {
   // maximum |value| per column ("name#f" float view, "name#u" integer view): bounds of
   // exact float sums (EVQL_FLOAT_SUM_EXACT)
   std::map<std::string, double> col_absmax;
+  // zone maps: unsigned minimum and maximum of every kZoneRows rows of a
+  // required unsigned / datetime column, built by the first query that prunes on it
+  // (16 B per 2048 rows; left out of evql_table_device_bytes)
+  struct ZoneMap {
+    evql::DevBuf<uint64_t> zmin, zmax;
+    uint64_t n_zones = 0;
+  };
+  std::map<std::string, ZoneMap> zone_maps;
   // required UINT64_PLAIN columns are kept narrow from this many rows on (~0 = never)
   uint64_t narrow_min_rows;
   // nested scans: column flattened to one value per output row of the scans whose
@@ -359,6 +368,11 @@ struct evql_query {
   // tables' sets for the groups this query now holds); PARTIAL rows read their values here
   uint64_t* d_mset[4] = {nullptr, nullptr, nullptr, nullptr};
   uint64_t mset_cap[4] = {0, 0, 0, 0};
+  // zone maps: the bitmap of excluded zones of this query's pruning conjuncts, built once by
+  // query_prepare; `tile_skip` is what the kernels get: NULL when no zone is excluded
+  evql::DevBuf<uint32_t> d_zone_bits;
+  const uint32_t* tile_skip = nullptr;
+  evql_zone_stats_t zstats{};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool probed = false;    // cardinality probe done (plans without groups_hint)
   bool keep_table = false;  // launch without emptying the group table / counters (the
@@ -502,6 +516,15 @@ Status materialize_nested_zip(evql_query* q, const std::vector<ColAccess>& cols,
 Status materialize_within_record(evql_query* q);
 Status expand_record_filter(evql_query* q, const LeafLevels* leaf);
 Status apply_where_resets(evql_query* q, const LeafLevels* leaf);
+
+// zone_maps.cc
+// the (cached) zone statistics of flat column `name`; EVQL_EARG when it does not qualify
+Status table_zone_map(evql_table* t, const std::string& name, const evql_table::ZoneMap** out);
+bool zone_column_qualifies(const ColumnLayout& cl);
+// query_prepare: statistics of the pruning columns -> q->d_zone_bits / tile_skip
+Status query_zone_select(evql_query* q);
+// tiles of the last launch / skipped tiles -> q->zstats
+void zone_stats_after_run(evql_query* q, uint64_t ntiles, uint64_t skipped);
 
 // value_bounds.cc
 Status choose_exact_sum_scales(evql_query* q);

@@ -268,6 +268,16 @@ int evql_table_download_image(const evql_table_t* t, void* dst, uint64_t len);
  * operators touch new columns; what a memory budget should count, not the file size. */
 uint64_t evql_table_device_bytes(const evql_table_t* t);
 
+/* Zone map of a flat column: the unsigned minimum and maximum of every 2048 rows (zones
+ * aligned to row 0; the last one may be partial).  Built on the device on first use --
+ * by this call or by the first query whose WHERE prunes on the column -- and cached on the
+ * table (16 bytes per zone; not part of evql_table_device_bytes).  *n receives the number of
+ * zones; the first min(cap, *n) of each are copied to zmin / zmax (either may be NULL).
+ * EVQL_EARG for a column that does not qualify: only required (not nullable, not
+ * repeated) unsigned-integer and datetime columns do. */
+int evql_table_zone_map(evql_table_t* t, const char* column, uint64_t* zmin, uint64_t* zmax,
+                        size_t cap, size_t* n);
+
 /*
  * Synthetic table generated directly into HBM in cstable v0.2.0 page layout
  * (the same bytes TableWriter would produce), SURVEY.md 8c(ii)/8d:
@@ -568,6 +578,25 @@ typedef struct {
                               * first execute estimated (0 = no estimate made) */
 } evql_query_stats_t;
 int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out);
+
+/* Zone maps, last execute.  Top-level AND conjuncts `column <op> literal` of WHERE
+ * (= < <= > >=, either operand order) over required unsigned / datetime columns of a flat
+ * scan exclude the zones whose [min, max] cannot hold a passing row; the kernels skip the
+ * row tiles whose zones are all excluded without reading them.  Results, rows_scanned and
+ * rows_passed are the same as without.  A WHERE that can raise (an integer division whose
+ * divisor is not a non-zero literal) prunes nothing.  The environment variable
+ * EVQL_ZONE_MAPS=0, read when the query is created, switches the feature off.  Over a
+ * chain the counts are the sums over its files. */
+typedef struct {
+  uint32_t conjuncts_used;  /* pruning conjuncts of the plan (at most 4); 0 = no pruning */
+  uint32_t zone_rows;       /* 2048 */
+  uint64_t zones_total;     /* zones of the table(s) */
+  uint64_t zones_excluded;  /* ... that no row can pass in */
+  uint64_t tile_rows;       /* rows per kernel tile of the last execute */
+  uint64_t tiles_total;     /* tiles covering the scanned row range */
+  uint64_t tiles_skipped;   /* ... that were not read */
+} evql_zone_stats_t;
+int evql_query_zone_stats(const evql_query_t* q, evql_zone_stats_t* out);
 
 /* the generated HIP source of the fused kernel (inspection / tests) */
 const char* evql_query_kernel_source(const evql_query_t* q);

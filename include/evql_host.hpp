@@ -152,6 +152,13 @@ class GpuGroupByScan : public TableExpression {
 
   evql_query_t* handle() { return query_; }
 
+  // what zone maps pruned in the last execute (evql_query_zone_stats)
+  evql_zone_stats_t zoneStats() const {
+    evql_zone_stats_t z{};
+    if (evql_query_zone_stats(query_, &z) != EVQL_OK) throw std::runtime_error(evql_last_error());
+    return z;
+  }
+
   // Fuses LimitExpression(limit, offset, OrderByExpression(specs, this)) into the
   // operator (orderby.cc:60-160, limit.cc:52-125); limit < 0 = ORDER BY only.
   // Throws NotLowerable when the first sort key cannot be read on the device, in
