@@ -609,7 +609,9 @@ class Merge:
 
 def compile_only(plan, columns, cache_dir=None):
     """compile the fused kernel of `plan` for gfx950 without a device.
-    columns: list of dict(name, logical_type, storage_type, dlevel_max=0, bits=0)"""
+    columns: list of dict(name, logical_type, storage_type, dlevel_max=0, bits=0,
+    narrow_bits=0); bits = width of a bit-packed file column, narrow_bits = 8 / 16 / 32: a
+    required UINT64_PLAIN / LEB128 column as read from the flat narrow copy a table keeps"""
     infos = (K.ColumnInfo * len(columns))()
     for i, c in enumerate(columns):
         infos[i].name = c["name"].encode()
@@ -618,7 +620,7 @@ def compile_only(plan, columns, cache_dir=None):
         infos[i].column_id = i + 1
         infos[i].dlevel_max = c.get("dlevel_max", 0)
         infos[i].rlevel_max = c.get("rlevel_max", 0)
-        infos[i].payload_bytes = c.get("bits", 0)
+        infos[i].payload_bytes = c.get("narrow_bits", 0) or c.get("bits", 0)
     size = C.c_size_t()
     cd = (cache_dir or KERNEL_CACHE_DIR).encode()
     _check(lib().evql_compile_only(C.byref(plan.desc), infos, len(columns), cd, C.byref(size)))

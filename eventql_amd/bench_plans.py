@@ -75,9 +75,9 @@ def precompile_all():
         compile_only(p, PLAIN_COLUMNS)
     compile_only(config4s(), STRING_KEY_COLUMNS)
     # the same shapes over the narrow copies a table of benchmark size keeps of its PLAIN
-    # integer columns (k < 1000, a, b < 65536: 16-bit pages; u < 1e7: 32-bit pages) -- the
-    # kernel source depends on the accessor and its width only, not on where the pages lie
-    narrow = [dict(c, storage_type=K.ENC_UINT32_BITPACKED, bits=32 if c["name"] == "u" else 16)
+    # integer columns (k < 1000, a, b < 65536: 16-bit arrays; u < 1e7: a 32-bit array) -- the
+    # kernel source depends on the accessor and its width only
+    narrow = [dict(c, narrow_bits=32 if c["name"] == "u" else 16)
               if c["storage_type"] == K.ENC_UINT64_PLAIN else c for c in PLAIN_COLUMNS]
     for p in (config2(), config3(), config4()):
         compile_only(p, narrow)

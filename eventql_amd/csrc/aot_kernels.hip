@@ -14,6 +14,7 @@ __device__ __forceinline__ u64 rt_column_value(const u8* image, const RtColumn& 
     case 0: return evql_plain64(image, (const u64*) c.pages, i);
     case 1: return evql_plain32(image, (const u64*) c.pages, i);
     case 2: return evql_bitpacked_rt(image, (const u64*) c.pages, c.bits, i);
+    case 4: return evql_narrow_rt(c.base, c.bits, i);  // the flat array of a narrow copy
     default: return c.soa[i];
   }
 }
@@ -1048,7 +1049,7 @@ __global__ void __launch_bounds__(kBlock) k_zone_minmax(const u8* image, RtColum
     for (int k = 0; k < 2; ++k) {
       const u64 r = base + ((u64) (k * kBlock) + tid) * 4;
       if (r + 3 < n) {
-        const u8* p = img + pages[r >> 17] + ((r & 0x1ffffull) << 2);
+        const u8* p = img + evql_page(pages, r >> 17) + ((r & 0x1ffffull) << 2);
         const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
         zone_take(q.x, lo, hi);
         zone_take(q.y, lo, hi);
@@ -1058,7 +1059,32 @@ __global__ void __launch_bounds__(kBlock) k_zone_minmax(const u8* image, RtColum
         for (u64 j = r; j < n && j < r + 4; ++j) zone_take(evql_plain32(img, pages, j), lo, hi);
       }
     }
-  } else {  // bit-packed pages (in place or a narrow copy), 8-byte SoA
+  } else if (col.mode == 4) {  // the flat array of a narrow copy: 8 values per thread
+    const u64 r = base + (u64) tid * 8;
+    const u32 vb = col.bits >> 3;  // bytes per value: a load of 8 values is naturally aligned
+    if (r + 7 < n) {
+      u32 w[8];
+      if (vb == 1) {
+        const evql_u32x2 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2*>(col.base + r));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = ((j < 4 ? q.x : q.y) >> (8 * (j & 3))) & 0xffu;
+      } else if (vb == 2) {
+        const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(col.base + 2 * r));
+        const u32 d[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = (d[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      } else {
+        const evql_u32x4* p = reinterpret_cast<const evql_u32x4*>(col.base + 4 * r);
+        const evql_u32x4 q0 = __builtin_nontemporal_load(p), q1 = __builtin_nontemporal_load(p + 1);
+        w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w;
+        w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) zone_take(w[j], lo, hi);
+    } else {
+      for (u64 j = r; j < n && j < r + 8; ++j) zone_take(evql_narrow_rt(col.base, col.bits, j), lo, hi);
+    }
+  } else {  // bit-packed pages, 8-byte SoA
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const u64 r = base + (u64) (k * kBlock) + tid;
@@ -2815,54 +2841,39 @@ __global__ void __launch_bounds__(kBlock) k_wr_bitpack(u8* image, const u64* pag
   *reinterpret_cast<u32*>(dst) = word;
 }
 
-// A required UINT64_PLAIN column of the image (65,536 values per page, pages wherever the
-// file put them) once more as the bit-packed pages k_wr_bitpack writes, of width 8 / 16 /
-// 32, for values known to fit `bits`.  One wave per block of 128 values: lane L reads
-// values 2L and 2L + 1 with one 16-byte load (1 KiB contiguous per wave and block), the
-// lanes exchange the low words so that lane j holds output word j of the block -- word w
-// of libsimdcomp lane l sits at index 4w + l and packs the values 4k + l,
-// k = w * 32 / bits .. -- and the block leaves as one contiguous store of 16 * bits bytes.
-__global__ void __launch_bounds__(kBlock) k_narrow_plain64(const u8* image, const u64* src_pages,
-                                                           u8* dst, const u64* dst_pages, u64 n,
-                                                           u32 bits) {
-  const u32 lane = threadIdx.x & 63u;
-  const u64 wave = ((u64) blockIdx.x * kBlock + threadIdx.x) >> 6;
-  const u64 nwaves = ((u64) gridDim.x * kBlock) >> 6;
-  const u64 nblocks = (n + 127) / 128;
-  const u32 w = lane >> 2, l = lane & 3u;
-  for (u64 blk = wave; blk < nblocks; blk += nwaves) {
-    const u64 r = blk * 128 + 2 * lane;
-    u32 x0 = 0, x1 = 0;
-    if (r < n) {  // (r is even: r + 1 lies in the same source page)
-      const u8* p = image + src_pages[r / kPlain64PageValues] + ((r % kPlain64PageValues) << 3);
+// The flat array of a narrow copy (evql_narrow_x2) of `n` values known to fit `bits` = 8 /
+// 16 / 32: value i at dst + i * bits / 8.  Source: a required UINT64_PLAIN column of the
+// image (65,536 values per page, pages wherever the file put them) or, src_pages == NULL,
+// the u64 array `values`.  A thread takes rows r, r + 1 (r even: both lie in one source
+// page) -- one 16-byte non-temporal load from a page -- and stores them as one word of
+// 2 * bits / 8 bytes; behind an odd n it stores a zero.  Consecutive lanes read and write
+// consecutive addresses.
+__global__ void __launch_bounds__(kBlock) k_narrow_flat(const u8* image, const u64* src_pages,
+                                                        const u64* values, u8* dst, u64 n,
+                                                        u32 bits) {
+  const u64 npairs = (n + 1) / 2;
+  for (u64 pi = (u64) blockIdx.x * kBlock + threadIdx.x; pi < npairs; pi += (u64) gridDim.x * kBlock) {
+    const u64 r = 2 * pi;
+    u32 x0, x1 = 0;
+    if (src_pages) {
+      const u8* p = image + evql_page(src_pages, r / kPlain64PageValues) + ((r % kPlain64PageValues) << 3);
       const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
       x0 = q.x;
-      x1 = r + 1 < n ? q.z : 0u;
+      if (r + 1 < n) x1 = q.z;
+    } else {
+      x0 = (u32) values[r];
+      if (r + 1 < n) x1 = (u32) values[r + 1];
     }
-    const u64 page = blk >> 10;
-    u8* out = dst + dst_pages[page] + (page == 0 ? 4 : 0) + (blk & 1023ull) * (16 * bits);
-    if (bits == 32) {  // word 4w + l = value 4w + l
-      // (`out` is 4 mod 8 behind the page header: evql_u32x2 is declared aligned(4))
-      static_assert(alignof(evql_u32x2) == 4, "dword-aligned 8-byte store");
-      evql_u32x2 o;
+    if (bits == 32) {
+      typedef u32 u32x2n __attribute__((ext_vector_type(2)));
+      u32x2n o;
       o.x = x0;
       o.y = x1;
-      *reinterpret_cast<evql_u32x2*>(out + 8 * lane) = o;
-    } else if (bits == 16) {  // values 8w + l and 8w + 4 + l
-      const int a = (int) (4 * w + (l >> 1));
-      const u32 a0 = __shfl(x0, a, 64), a1 = __shfl(x1, a, 64);
-      const u32 b0 = __shfl(x0, a + 2, 64), b1 = __shfl(x1, a + 2, 64);
-      const u32 va = (l & 1u) ? a1 : a0, vb = (l & 1u) ? b1 : b0;
-      *reinterpret_cast<u32*>(out + 4 * lane) = (va & 0xffffu) | (vb << 16);
-    } else {  // 8 bits: 32 words, values 16w + l + 4m, m = 0 .. 3
-      const int a = (int) (8 * (w & 7u) + (l >> 1));
-      u32 word = 0;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const u32 m0 = __shfl(x0, a + 2 * m, 64), m1 = __shfl(x1, a + 2 * m, 64);
-        word |= (((l & 1u) ? m1 : m0) & 0xffu) << (8 * m);
-      }
-      if (lane < 32) *reinterpret_cast<u32*>(out + 4 * lane) = word;
+      *reinterpret_cast<u32x2n*>(dst + 8 * pi) = o;
+    } else if (bits == 16) {
+      *reinterpret_cast<u32*>(dst + 4 * pi) = (x0 & 0xffffu) | (x1 << 16);
+    } else {
+      *reinterpret_cast<unsigned short*>(dst + 2 * pi) = (unsigned short) ((x0 & 0xffu) | ((x1 & 0xffu) << 8));
     }
   }
 }
@@ -3163,14 +3174,14 @@ hipError_t launch_wr_compact(const uint64_t* values, const uint8_t* nulls,
   return hipGetLastError();
 }
 
-hipError_t launch_narrow_plain64(const uint8_t* image, const uint64_t* src_pages, uint8_t* dst,
-                                 const uint64_t* dst_pages, uint64_t n, uint32_t bits,
-                                 hipStream_t s) {
+hipError_t launch_narrow_flat(const uint8_t* image, const uint64_t* src_pages,
+                              const uint64_t* values, uint8_t* dst, uint64_t n, uint32_t bits,
+                              hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const u64 nblocks = (n + 127) / 128;  // one wave each, grid-stride
-  hipLaunchKernelGGL(k_narrow_plain64, dim3(grid_for(nblocks * 64, kBlock, 16384)), dim3(kBlock), 0,
-                     s, (const u8*) image, (const u64*) src_pages, (u8*) dst,
-                     (const u64*) dst_pages, (u64) n, (u32) bits);
+  if (bits != 8 && bits != 16 && bits != 32) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_narrow_flat, dim3(grid_for((n + 1) / 2, kBlock, 65536)), dim3(kBlock), 0, s,
+                     (const u8*) image, (const u64*) src_pages, (const u64*) values, (u8*) dst,
+                     (u64) n, (u32) bits);
   return hipGetLastError();
 }
 

@@ -179,7 +179,6 @@ uint64_t evql_table_device_bytes(const evql_table_t* t) {
     add(m.d_tags);
     add(m.d_strpos);
     add(m.d_packed);
-    add(m.d_packed_pages);
   }
   // (zone maps are not counted: 16 B per 2048 rows, and a plan with a range conjunct over a
   // table without narrow copies leaves this figure where it was)
@@ -192,7 +191,6 @@ uint64_t evql_table_device_bytes(const evql_table_t* t) {
     add(kv.second.d_values.p);
     add(kv.second.d_hash.p);
     add(kv.second.d_packed.p);
-    add(kv.second.d_packed_pages.p);
   }
   for (const auto& kv : t->leaf_cache) {
     add(kv.second.levels.p);
@@ -784,7 +782,9 @@ int evql_query_stats(const evql_query_t* q, evql_query_stats_t* out) {
   *out = q->stats;
   uint64_t bytes = 0;
   // per column what the kernel streams: the file's payload, or the narrow copy the table
-  // keeps of it (LEB128 / PLAIN columns as bit-packed pages) where that is smaller
+  // keeps of it (LEB128 / PLAIN columns as flat narrow arrays: the maximum word and whole
+  // blocks of 128 values, the figure the copy has always been accounted at) where that is
+  // smaller
   auto column_bytes = [](const evql_query* p, const ColAccess& c) -> uint64_t {
     const uint64_t file = p->table->payload_bytes[c.layout_index];
     if (!c.packed || p->nested) return file;
@@ -1016,9 +1016,24 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
   bool unsupported = false;
   Status st = build_kernel_plan(layout, plan, &q, &unsupported);
   if (!st.ok()) return ret(st);
-  // bit widths are not known without pages: payload_bytes carries the width
+  // bit widths are not known without pages: payload_bytes carries the width.  On a required
+  // UINT64_PLAIN / UINT64_LEB128 column a width of 8 / 16 / 32 asks for the shape over the
+  // flat narrow copy a resident table keeps of it (query_prepare makes the same switch).
   for (auto& c : q.kp.cols) {
-    if (c.mode == ColAccess::BITPACKED) c.bits = uint32_t(columns[c.layout_index].payload_bytes);
+    const evql_column_info_t& ci = columns[c.layout_index];
+    const uint32_t w = uint32_t(ci.payload_bytes);
+    if (c.mode == ColAccess::BITPACKED) {
+      c.bits = w;
+    } else if ((w == 8 || w == 16 || w == 32) && ci.dlevel_max == 0 && ci.rlevel_max == 0 &&
+               (c.stype != EVQL_T_FLOAT64 || c.from_uint_to_float) &&
+               ((c.mode == ColAccess::PLAIN64 &&
+                 ColumnEncoding(ci.storage_type) == ColumnEncoding::UINT64_PLAIN) ||
+                (c.mode == ColAccess::SOA &&
+                 ColumnEncoding(ci.storage_type) == ColumnEncoding::UINT64_LEB128))) {
+      c.mode = ColAccess::NARROW;
+      c.bits = w;
+      c.packed = true;
+    }
   }
   q.source = generate_kernel_source(&q.kp);
   std::vector<char> code;

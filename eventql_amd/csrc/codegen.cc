@@ -85,7 +85,7 @@ struct Emitter {
     if (e->type != EVQL_T_UINT64 && e->type != EVQL_T_TIMESTAMP64) return false;
     const ColAccess& c = (*cols)[e->input];
     if (c.stype != e->type) return false;
-    return c.mode == ColAccess::PLAIN32 ||
+    return c.mode == ColAccess::PLAIN32 || c.mode == ColAccess::NARROW ||
            (c.mode == ColAccess::BITPACKED && c.bits >= 1 && c.bits <= 32);
   }
   // Compare of a narrow unsigned column with a pooled literal.  With the constant in the

@@ -11,17 +11,18 @@ namespace evql {
 
 // how the fused kernel reads one scan column
 struct ColAccess {
-  enum Mode { PLAIN64 = 0, PLAIN32 = 1, BITPACKED = 2, SOA = 3 };
+  // NARROW: the table's flat narrow copy of a LEB128 / PLAIN integer column (bits = 8 / 16 / 32)
+  enum Mode { PLAIN64 = 0, PLAIN32 = 1, BITPACKED = 2, SOA = 3, NARROW = 4 };
   std::string name;
   uint32_t stype = EVQL_T_NIL;  // evql_stype seen by the VM
   Mode mode = PLAIN64;
-  uint32_t bits = 0;          // BITPACKED width
+  uint32_t bits = 0;          // BITPACKED / NARROW width
   bool has_tags = false;      // SOA with a tag byte array (nullable column)
   bool bool_normalize = false;  // BOOLEAN column: value = (raw > 0)
   bool from_uint_to_float = false;  // FLOAT64 stype over a uint column: (double) u
   bool string_hash = false;   // STRING column materialised as hash64
   bool string_bytes = false;  // ... and compared bytewise on the device (strpos array)
-  bool packed = false;        // BITPACKED over the table's narrow copy (LEB128 / PLAIN column)
+  bool packed = false;        // NARROW: read from the narrow copy, not from the file's pages
   bool dict_code = false;     // PLAIN32 over the table's dictionary codes of a STRING column
   int layout_index = -1;      // index into TableLayout::columns
 };

@@ -347,6 +347,11 @@ struct Gen {
           s << ind << "  evql_bitpacked_x2<" << c.bits << ">(A.col[" << i << "].base, A.col[" << i << "].pages, r, x"
             << i << "[u][0], x" << i << "[u][1]);\n";
           break;
+        case ColAccess::NARROW:
+          // (the page-less overload of the width's accessor: evql_narrow_x2)
+          s << ind << "  evql_bitpacked_x2<" << c.bits << ">(A.col[" << i << "].base, r, x" << i
+            << "[u][0], x" << i << "[u][1]);\n";
+          break;
         case ColAccess::SOA:
           s << ind << "  evql_soa_x2(A.col[" << i << "].soa, r, x" << i << "[u][0], x" << i
             << "[u][1]);\n";

@@ -42,8 +42,9 @@ struct EvqlColArg {
   // STRING columns compared bytewise: per row (len << 40) | position of the first
   // byte in the column's logical byte stream (pages laid end to end), or NULL
   const u64* strpos;
-  // where `pages` offsets count from: the file image, or the private buffer of a
-  // column the runtime keeps a narrow bit-packed copy of (LEB128 / PLAIN integers)
+  // where `pages` offsets count from: the file image or a dictionary's code array; or
+  // the flat narrow copy the runtime keeps of the column (LEB128 / PLAIN integers,
+  // evql_narrow_x2), which has no page table
   const u8* base;
 };
 
@@ -143,10 +144,22 @@ __device__ __forceinline__ u64 evql_ident_word(u64 x) { return x == ~0ull ? ~0ul
 typedef u32 evql_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef u32 evql_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
 
+// Entry i of a column's page table, read through the constant address space: where i is
+// uniform over the wave (the tile loops: a tile never crosses a page) the lookup is one
+// scalar load -- off vmcnt, no VGPR address, and the column loads behind it take the SGPR
+// base form instead of waiting for a vector load of the offset.  A divergent i (gathers,
+// string compares) still compiles to an ordinary vector load.  The cast relies on this:
+// page tables are written when a table is opened, packed or flattened, on the stream of
+// the kernels that read them and before any of them is launched, and never while one runs.
+__device__ __forceinline__ u64 evql_page(const u64* pages, u64 i) {
+  typedef const u64 __attribute__((address_space(4))) * evql_cu64p;
+  return ((evql_cu64p) (u64) pages)[i];
+}
+
 // two consecutive 8-byte values (rows r, r+1; r even) of a PLAIN u64/f64 column
 __device__ __forceinline__ void evql_plain64_x2(const u8* image, const u64* pages,
                                                 u64 r, u64& v0, u64& v1) {
-  const u8* p = image + pages[r >> 16] + ((r & 0xffffull) << 3);
+  const u8* p = image + evql_page(pages, r >> 16) + ((r & 0xffffull) << 3);
   // column pages are streamed once: non-temporal loads (measured on MI355X, 32 GB
   // pure-read stream: 6.0-6.1 TB/s with plain loads, 6.5-6.8 TB/s non-temporal)
   evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
@@ -155,7 +168,7 @@ __device__ __forceinline__ void evql_plain64_x2(const u8* image, const u64* page
 }
 
 __device__ __forceinline__ u64 evql_plain64(const u8* image, const u64* pages, u64 r) {
-  const u8* p = image + pages[r >> 16] + ((r & 0xffffull) << 3);
+  const u8* p = image + evql_page(pages, r >> 16) + ((r & 0xffffull) << 3);
   evql_u32x2 q = *reinterpret_cast<const evql_u32x2*>(p);
   return (u64) q.x | ((u64) q.y << 32);
 }
@@ -163,14 +176,14 @@ __device__ __forceinline__ u64 evql_plain64(const u8* image, const u64* pages, u
 // UINT32_PLAIN: 131072 values per 512 KiB page
 __device__ __forceinline__ void evql_plain32_x2(const u8* image, const u64* pages,
                                                 u64 r, u64& v0, u64& v1) {
-  const u8* p = image + pages[r >> 17] + ((r & 0x1ffffull) << 2);
+  const u8* p = image + evql_page(pages, r >> 17) + ((r & 0x1ffffull) << 2);
   evql_u32x2 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2*>(p));
   v0 = q.x;
   v1 = q.y;
 }
 
 __device__ __forceinline__ u64 evql_plain32(const u8* image, const u64* pages, u64 r) {
-  const u8* p = image + pages[r >> 17] + ((r & 0x1ffffull) << 2);
+  const u8* p = image + evql_page(pages, r >> 17) + ((r & 0x1ffffull) << 2);
   return *reinterpret_cast<const u32*>(p);
 }
 
@@ -204,7 +217,7 @@ __device__ __forceinline__ u32 evql_bitpacked(const u8* image, const u64* pages,
   if (B == 0) return 0;
   const u64 page = i >> 17;  // 1024 blocks * 128 values
   const u32 j = (u32) (i & 0x1ffffull);
-  const u8* base = image + pages[page] + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
+  const u8* base = image + evql_page(pages, page) + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
   const u32 i7 = j & 127u, l = i7 & 3u, k = i7 >> 2;
   const u32 p = k * B, w = p >> 5, s = p & 31u;
   const u32* W = reinterpret_cast<const u32*>(base);
@@ -227,7 +240,7 @@ __device__ __forceinline__ void evql_bitpacked_x2(const u8* image, const u64* pa
   typedef u32 evql_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
   const u64 page = i >> 17;
   const u32 j = (u32) (i & 0x1ffffull);
-  const u8* base = image + pages[page] + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
+  const u8* base = image + evql_page(pages, page) + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
   const u32 i7 = j & 127u, l = i7 & 3u, k = i7 >> 2;  // l is 0 or 2
   const u32 p = k * B, w = p >> 5, s = p & 31u;
   const u32* W = reinterpret_cast<const u32*>(base) + 4 * w + l;
@@ -257,13 +270,57 @@ __device__ __forceinline__ u32 evql_bitpacked_rt(const u8* image, const u64* pag
   if (B == 0) return 0;
   const u64 page = i >> 17;
   const u32 j = (u32) (i & 0x1ffffull);
-  const u8* base = image + pages[page] + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
+  const u8* base = image + evql_page(pages, page) + (page == 0 ? 4 : 0) + (u64) (j >> 7) * (16 * B);
   const u32 i7 = j & 127u, l = i7 & 3u, k = i7 >> 2;
   const u32 p = k * B, w = p >> 5, s = p & 31u;
   const u32* W = reinterpret_cast<const u32*>(base);
   u64 v = (u64) W[4 * w + l] >> s;
   if (s + B > 32) v |= (u64) W[4 * (w + 1) + l] << (32 - s);
   return evql_opaque((u32) (v & (B >= 32 ? 0xffffffffull : ((1ull << B) - 1))));
+}
+
+// A narrow copy the runtime keeps of a small-valued integer column (table.cc pack_narrow /
+// narrow_plain_column): a flat little-endian array of B / 8 bytes per value (B = 8, 16,
+// 32) in row order that starts 256-byte aligned, zero behind the last row for more than a
+// tile.  Rows r, r + 1 (r even) are one non-temporal load of 2 * B / 8 bytes at its natural
+// alignment: no page table, no header, every byte requested once.  The results stay
+// evql_opaque: the `% 13` narrowing above applies to any value of known range.
+template <int B>
+__device__ __forceinline__ void evql_narrow_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+  static_assert(B == 8 || B == 16 || B == 32, "narrow copies are 8, 16 or 32 bits wide");
+  u32 a, b;
+  if (B == 32) {
+    typedef u32 evql_u32x2n __attribute__((ext_vector_type(2)));
+    const evql_u32x2n q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2n*>(base + (r << 2)));
+    a = q.x;
+    b = q.y;
+  } else if (B == 16) {
+    const u32 q = __builtin_nontemporal_load(reinterpret_cast<const u32*>(base + (r << 1)));
+    a = q & 0xffffu;
+    b = q >> 16;
+  } else {
+    const u32 q = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(base + r));
+    a = q & 0xffu;
+    b = q >> 8;
+  }
+  v0 = evql_opaque(a);
+  v1 = evql_opaque(b);
+}
+
+// What the generated text calls: it names a column's accessor by its width whether the bits
+// lie in libsimdcomp pages of the file (base, pages, i) or in a flat narrow copy (base, i).
+template <int B>
+__device__ __forceinline__ void evql_bitpacked_x2(const u8* flat, u64 i, u64& a, u64& b) {
+  evql_narrow_x2<B>(flat, i, a, b);
+}
+
+// value i of a narrow copy of runtime width (decode / gather kernels)
+__device__ __forceinline__ u32 evql_narrow_rt(const u8* base, u32 B, u64 i) {
+  u32 v;
+  if (B == 32) v = reinterpret_cast<const u32*>(base)[i];
+  else if (B == 16) v = reinterpret_cast<const unsigned short*>(base)[i];
+  else v = base[i];
+  return evql_opaque(v);
 }
 
 __device__ __forceinline__ bool evql_row_filter(const u8* bits, u64 len, u64 row) {
@@ -290,7 +347,7 @@ __device__ __forceinline__ EvqlStr evql_lit_str(const u8* bytes, u32 len) {
 }
 __device__ __forceinline__ u32 evql_str_byte(const EvqlStr& s, u32 i) {
   const u64 p = s.pos + i;
-  return s.pages ? s.base[s.pages[p >> 19] + (p & 0x7ffffu)] : s.base[p];
+  return s.pages ? s.base[evql_page(s.pages, p >> 19) + (p & 0x7ffffu)] : s.base[p];
 }
 // memcmp-equality (eq_string / neq_string)
 __device__ __forceinline__ bool evql_str_eq(const EvqlStr& a, const EvqlStr& b) {

@@ -539,7 +539,7 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
         rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
       } else if (ca.packed) {
         const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = m.d_packed_pages;
+        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
         rc[c].base = m.d_packed;
       } else if (ca.mode == ColAccess::SOA) {
         const MaterializedColumn& m = t->materialized[ca.name];
@@ -990,13 +990,13 @@ Status chain_merge(evql_query* head) {
         // first rows of a nested scan are FLATTENED rows: the operator's own columns
         // (fetch_results gathers from the same sources)
         if (ca.packed) {
-          rc[c].pages = q->nested_packed[c].pages;
+          rc[c].pages = nullptr;
           rc[c].base = q->nested_packed[c].base;
         }
         rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
       } else if (ca.packed) {
         const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = m.d_packed_pages;
+        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
         rc[c].base = m.d_packed;
       } else if (ca.mode == ColAccess::SOA) {
         const MaterializedColumn& m = t->materialized[ca.name];

@@ -174,7 +174,7 @@ Status query_prepare(evql_query* q) {
   q->nested_packed.assign(q->kp.cols.size(), evql_query::PackedSource{});
   if (q->nested && !q->within_record && !q->nested_where_mixed && q->nested_leaf >= 0) {
     // The fused kernel streams the flattened columns; like required LEB128 columns they
-    // are kept once more as bit-packed pages of 8 / 16 / 32 bits where their maximum
+    // are kept once more as flat arrays of 8 / 16 / 32 bits per value where their maximum
     // fits (config 5: 1 + 4 bytes per row instead of 8 + 8).  Not for string hashes,
     // nor when WHERE resets rewrite the columns per query (apply_where_resets).
     for (size_t i = 0; i < q->kp.cols.size(); ++i) {
@@ -185,16 +185,14 @@ Status query_prepare(evql_query* q) {
       evql_table::NestedFlat& e = hit->second;
       if (!e.pack_tried) {
         e.pack_tried = true;
-        Status stp = pack_narrow(q->ctx->stream, e.d_values, e.nflat, &e.d_packed, &e.d_packed_pages,
-                                 &e.packed_bits);
+        Status stp = pack_narrow(q->ctx->stream, e.d_values, e.nflat, &e.d_packed, &e.packed_bits);
         if (!stp.ok()) return stp;
       }
       if (!e.packed_bits) continue;
-      c.mode = ColAccess::BITPACKED;
+      c.mode = ColAccess::NARROW;
       c.bits = e.packed_bits;
       c.packed = true;
       q->nested_packed[i].base = e.d_packed;
-      q->nested_packed[i].pages = e.d_packed_pages;
       repacked = true;
     }
   }
@@ -206,7 +204,7 @@ Status query_prepare(evql_query* q) {
         cl.dlevel_max == 0 && (c.stype != EVQL_T_FLOAT64 || c.from_uint_to_float) &&
         t->layout.num_rows >= t->narrow_min_rows) {
       // A required UINT64_PLAIN column of a table that stays resident: kept once more as
-      // bit-packed pages of 8 / 16 / 32 bits where its maximum fits, like a LEB128 column
+      // a flat array of 8 / 16 / 32 bits per value where its maximum fits, like a LEB128 column
       // (DESIGN.md 3.3).  The maximum comes from the cached statistics pass; the copy is
       // made by the first operator that references the column.
       auto hit = t->materialized.find(c.name);
@@ -221,7 +219,7 @@ Status query_prepare(evql_query* q) {
         }
       }
       if (hit != t->materialized.end() && hit->second.packed_bits) {
-        c.mode = ColAccess::BITPACKED;
+        c.mode = ColAccess::NARROW;
         c.bits = hit->second.packed_bits;
         c.packed = true;
         repacked = true;
@@ -233,8 +231,8 @@ Status query_prepare(evql_query* q) {
       Status st = materialize_column(t, c);
       if (!st.ok()) return st;
       const MaterializedColumn& m = t->materialized[c.name];
-      if (m.packed_bits) {  // LEB128 kept as narrow bit-packed pages
-        c.mode = ColAccess::BITPACKED;
+      if (m.packed_bits) {  // LEB128 kept as a flat narrow array
+        c.mode = ColAccess::NARROW;
         c.bits = m.packed_bits;
         c.packed = true;
         repacked = true;
@@ -425,11 +423,11 @@ void fill_host_args(evql_query* q, HostArgs* ap) {
       a.col[i].pages = d.d_code_pages;
       a.col[i].base = reinterpret_cast<const uint8_t*>(d.d_codes);
     } else if (c.packed && q->nested) {
-      a.col[i].pages = q->nested_packed[i].pages;
+      a.col[i].pages = nullptr;  // (ColAccess::NARROW: a flat array)
       a.col[i].base = q->nested_packed[i].base;
     } else if (c.packed) {
       const MaterializedColumn& m = t->materialized[c.name];
-      a.col[i].pages = m.d_packed_pages;
+      a.col[i].pages = nullptr;
       a.col[i].base = m.d_packed;
     }
     if (q->nested) {

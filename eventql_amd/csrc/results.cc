@@ -118,7 +118,7 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
       rc[c].bits = ca.bits;
       if (ca.packed) {
         const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = m.d_packed_pages;
+        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
         rc[c].base = m.d_packed;
       } else if (ca.mode == ColAccess::SOA) {
         const MaterializedColumn& m = t->materialized[ca.name];
@@ -392,11 +392,11 @@ static Status first_rows_from_table(evql_query* q, uint64_t n, uint32_t nwords) 
     rc[c].mode = ca.mode;
     rc[c].bits = ca.bits;
     if (ca.packed && q->nested) {
-      rc[c].pages = q->nested_packed[c].pages;
+      rc[c].pages = nullptr;
       rc[c].base = q->nested_packed[c].base;
     } else if (ca.packed) {
       const MaterializedColumn& m = t->materialized[ca.name];
-      rc[c].pages = m.d_packed_pages;
+      rc[c].pages = nullptr;
       rc[c].base = m.d_packed;
     }
     if (q->nested) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <string>
@@ -146,11 +147,10 @@ struct MaterializedColumn {
   uint64_t* d_values = nullptr;
   uint8_t* d_tags = nullptr;
   // a required UINT64_LEB128 or UINT64_PLAIN column (table.cc materialize_column /
-  // narrow_plain_column) kept as bit-packed pages of width 8 / 16 / 32 (the narrowest
-  // that holds the column's maximum; widths that divide 32 decode with one shift):
-  // the fused kernel then reads 1 - 4 bytes per value instead of an 8-byte SoA word
+  // narrow_plain_column) kept as a flat array of 8 / 16 / 32 bits per value (the narrowest
+  // that holds the column's maximum; layout: narrow_copy_bytes below): the fused kernel
+  // then reads 1 - 4 bytes per value instead of an 8-byte SoA word
   uint8_t* d_packed = nullptr;
-  uint64_t* d_packed_pages = nullptr;  // page offsets into d_packed
   uint32_t packed_bits = 0;
   bool string_hash = false;
   // strings: (len << 40) | byte position of the value in the column's page stream,
@@ -167,7 +167,6 @@ struct MaterializedColumn {
     std::swap(d_strpos, o.d_strpos);
     std::swap(string_hash, o.string_hash);
     std::swap(d_packed, o.d_packed);
-    std::swap(d_packed_pages, o.d_packed_pages);
     std::swap(packed_bits, o.packed_bits);
     return *this;
   }
@@ -176,7 +175,6 @@ struct MaterializedColumn {
     if (d_tags) hipFree(d_tags);
     if (d_strpos) hipFree(d_strpos);
     if (d_packed) hipFree(d_packed);
-    if (d_packed_pages) hipFree(d_packed_pages);
   }
 };
 
@@ -233,10 +231,9 @@ struct evql_table {
     evql::DevBuf<uint64_t> d_values;  // per row: value bits; strings: (len << 40 | position)
     uint64_t nflat = 0;
     evql::DevBuf<uint64_t> d_hash;    // strings: 64-bit hash of the row's bytes
-    // the values once more as bit-packed pages of 8 / 16 / 32 bits (when their maximum
+    // the values once more as a flat array of 8 / 16 / 32 bits each (when their maximum
     // fits): what the fused kernel streams instead of the 8-byte words
     evql::DevBuf<uint8_t> d_packed;
-    evql::DevBuf<uint64_t> d_packed_pages;
     uint32_t packed_bits = 0;
     bool pack_tried = false;
   };
@@ -329,10 +326,9 @@ struct evql_query {
   uint64_t nested_rows = 0;
   std::vector<uint64_t*> nested_flat;
   std::vector<uint64_t*> nested_strpos;  // string columns: (len << 40 | position) per row
-  // nested scans over narrow bit-packed copies of the flattened columns (ColAccess::packed)
+  // nested scans over flat narrow copies of the flattened columns (ColAccess::packed)
   struct PackedSource {
     const uint8_t* base = nullptr;
-    const uint64_t* pages = nullptr;
   };
   std::vector<PackedSource> nested_packed;
   int nested_leaf = -1;  // layout index of the leaf column of the scan
@@ -496,8 +492,23 @@ Status stream_bits(evql_table* t, const std::vector<PageRef>& pages, uint32_t* b
 // has one for LEB128 values, else it is allocated into `*owned`.
 Status defined_value_source(evql_table* t, int li, uint64_t nvalues, uint64_t* dst, RtColumn* src,
                             DevBuf<uint64_t>* owned);
+// A narrow copy (ColAccess::NARROW) of `n` values of `bits` = 8 / 16 / 32 bits is one
+// allocation: the little-endian values in row order from byte 0 (256-byte aligned, as the
+// allocator hands it out), zeros up to a whole number of kNarrowUnit values and through
+// kNarrowSlack bytes more, then the 4-byte maximum a value of that width can take.  A tile
+// of the fused kernels (at most 16384 rows, whole tiles from row 0) reads at most 64 KiB
+// behind the last row: zeros, inside the allocation, whatever `n`.
+static const uint64_t kNarrowUnit = 131072;
+static const uint64_t kNarrowSlack = 1ull << 20;
+inline uint64_t narrow_copy_max_word_at(uint64_t n, uint32_t bits) {
+  const uint64_t units = std::max<uint64_t>((n + kNarrowUnit - 1) / kNarrowUnit, 1);
+  return units * kNarrowUnit * (bits / 8) + kNarrowSlack;
+}
+inline uint64_t narrow_copy_bytes(uint64_t n, uint32_t bits) {
+  return narrow_copy_max_word_at(n, bits) + 256;
+}
 Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<uint8_t>* d_packed,
-                   DevBuf<uint64_t>* d_packed_pages, uint32_t* bits_out);
+                   uint32_t* bits_out);
 // Required UINT64_PLAIN columns kept narrow: in tables of at least
 // kNarrowMinRows rows (EVQL_NARROW_PLAIN overrides, read when a table becomes resident)
 static const uint64_t kNarrowMinRows = 1ull << 26;

@@ -219,36 +219,24 @@ static uint64_t fixed_width_capacity(const ColumnLayout& c) {
   }
 }
 
-// the zeroed buffer and page table of `n` values as bit-packed pages of width `bits`
-// (`zero_all` = false: only the header and what lies behind the last block -- the caller
-// writes every block in full)
-static Status alloc_narrow_pages(hipStream_t s, uint64_t n, uint32_t bits, bool zero_all,
-                                 DevBuf<uint8_t>* d_packed,
-                                 DevBuf<uint64_t>* d_packed_pages) {
-  const uint64_t nblocks = (n + 127) / 128;
-  const uint64_t page_bytes = 16ull * bits * kBitpackBlocksPerPage;
-  const uint64_t npages = (nblocks + kBitpackBlocksPerPage - 1) / kBitpackBlocksPerPage;
-  // a tile reads up to 8192 rows beyond the last one: zero slack like the image's
-  const uint64_t bytes = 4 + npages * page_bytes + (1 << 20);
+// the buffer of a narrow copy of `n` values of `bits` bits (runtime.h narrow_copy_bytes):
+// everything behind the value pairs that the caller's launch_narrow_flat writes is zeroed,
+// the maximum word stored
+static Status alloc_narrow_copy(hipStream_t s, uint64_t n, uint32_t bits, DevBuf<uint8_t>* d_packed) {
+  const uint64_t bytes = narrow_copy_bytes(n, bits);
   HIP_TRY(d_packed->alloc(bytes));
-  const uint64_t written = zero_all ? 0 : 4 + nblocks * 16ull * bits;
+  const uint64_t written = (n + 1) / 2 * 2 * (bits / 8);
   HIP_TRY(hipMemsetAsync(d_packed->p + written, 0, bytes - written, s));
-  std::vector<uint64_t> offs;
-  for (uint64_t pi = 0; pi < npages; ++pi) offs.push_back(pi == 0 ? 0 : 4 + pi * page_bytes);
-  offs.push_back(offs.back());  // (one past the end stays in bounds)
-  HIP_TRY(d_packed_pages->alloc(offs.size() * 8));
-  HIP_TRY(hipMemcpyAsync(d_packed_pages->p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
-  const uint32_t hdr = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-  HIP_TRY(hipMemcpyAsync(d_packed->p, &hdr, 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));  // (offs / hdr live until here)
+  const uint32_t maxw = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
+  HIP_TRY(hipMemcpyAsync(d_packed->p + narrow_copy_max_word_at(n, bits), &maxw, 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (maxw lives until here)
   return Status();
 }
 
-// `n` u64 values as bit-packed pages (libsimdcomp layout, 131,072 values per page) of the
-// narrowest of 8 / 16 / 32 bits that holds their maximum; *bits = 0 when it does not fit
-// 32 bits.  Widths dividing 32 never straddle a word: the decode is one shift and one mask.
+// `n` u64 values as a narrow copy of the narrowest of 8 / 16 / 32 bits that holds their
+// maximum; *bits = 0 when it does not fit 32 bits.
 Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<uint8_t>* d_packed,
-                   DevBuf<uint64_t>* d_packed_pages, uint32_t* bits_out) {
+                   uint32_t* bits_out) {
   *bits_out = 0;
   if (n == 0) return Status();
   DevBuf<uint64_t> d_max;
@@ -260,9 +248,9 @@ Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<u
   HIP_TRY(hipStreamSynchronize(s));
   if (maxv > 0xffffffffull) return Status();
   const uint32_t bits = maxv <= 0xffu ? 8 : (maxv <= 0xffffu ? 16 : 32);
-  Status st = alloc_narrow_pages(s, n, bits, true, d_packed, d_packed_pages);
+  Status st = alloc_narrow_copy(s, n, bits, d_packed);
   if (!st.ok()) return st;
-  HIP_TRY(launch_wr_bitpack(d_packed->p, d_packed_pages->p, d_values, nullptr, n, bits, s));
+  HIP_TRY(launch_narrow_flat(nullptr, nullptr, d_values, d_packed->p, n, bits, s));
   HIP_TRY(hipStreamSynchronize(s));
   *bits_out = bits;
   return Status();
@@ -278,13 +266,13 @@ uint64_t narrow_plain_min_rows() {
   return kNarrowMinRows;
 }
 
-// Required UINT64_PLAIN column `li`, whose maximum is `maxv`, once more as bit-packed pages
+// Required UINT64_PLAIN column `li`, whose maximum is `maxv`, once more as a narrow copy
 // of the narrowest of 8 / 16 / 32 bits -- t->materialized[name] with packed_bits set and no
 // 8-byte words, what a required LEB128 column leaves there.  The file's own pages stay
 // (download_image, the LSM paths and table_rt_column read them).  No entry when the
 // maximum does not fit 32 bits.
 Status narrow_plain_column(evql_table* t, int li, uint64_t maxv) {
-  static_assert(kPlain64PageValues == kPlainPageSize / 8, "k_narrow_plain64's source page size");
+  static_assert(kPlain64PageValues == kPlainPageSize / 8, "k_narrow_flat's source page size");
   const ColumnLayout& c = t->layout.columns[li];
   const uint64_t n = t->layout.num_rows;
   if (t->materialized.count(c.name) || maxv > 0xffffffffull || n == 0) return Status();
@@ -293,13 +281,11 @@ Status narrow_plain_column(evql_table* t, int li, uint64_t maxv) {
   const uint32_t bits = maxv <= 0xffu ? 8 : (maxv <= 0xffffu ? 16 : 32);
   MaterializedColumn m;
   DevBuf<uint8_t> d_packed;
-  DevBuf<uint64_t> d_packed_pages;
-  Status st = alloc_narrow_pages(s, n, bits, false, &d_packed, &d_packed_pages);
+  Status st = alloc_narrow_copy(s, n, bits, &d_packed);
   if (!st.ok()) return st;
-  HIP_TRY(launch_narrow_plain64(t->d_image, t->d_pages[li][0], d_packed.p, d_packed_pages.p, n, bits, s));
+  HIP_TRY(launch_narrow_flat(t->d_image, t->d_pages[li][0], nullptr, d_packed.p, n, bits, s));
   HIP_TRY(hipStreamSynchronize(s));
   m.d_packed = d_packed.release();
-  m.d_packed_pages = d_packed_pages.release();
   m.packed_bits = bits;
   t->materialized[c.name] = std::move(m);
   return Status();
@@ -451,20 +437,17 @@ Status materialize_column(evql_table* t, const ColAccess& ca) {
     HIP_TRY(hipStreamSynchronize(s));
   } else if (c.storage_type == ColumnEncoding::UINT64_LEB128 && n > 0) {
     // Required LEB128 column (the reference's default integer encoding,
-    // TableSchema.cc:290-316): keep it in HBM as bit-packed pages of the narrowest
-    // of 8 / 16 / 32 bits that holds its maximum instead of 8-byte words.  The fused
-    // kernel then streams fewer bytes than the LEB128 stream itself holds for
-    // multi-byte values, with a decode of one shift and one mask (widths dividing 32
-    // never straddle a word).  Decoding LEB128 inside the fused kernel instead would
+    // TableSchema.cc:290-316): keep it in HBM as a flat array of the narrowest of
+    // 8 / 16 / 32 bits per value that holds its maximum instead of 8-byte words.  The
+    // fused kernel then streams fewer bytes than the LEB128 stream itself holds for
+    // multi-byte values, with no decode but a zero extension.  Decoding LEB128 inside the fused kernel instead would
     // cost ~10 lane-operations per stream byte (terminator scan + extraction) against
     // the ~12 the chip has per HBM byte at 6.3 TB/s for the whole query.
     uint32_t bits = 0;
     DevBuf<uint8_t> d_packed;
-    DevBuf<uint64_t> d_packed_pages;
-    Status stp = pack_narrow(s, m.d_values, n, &d_packed, &d_packed_pages, &bits);
+    Status stp = pack_narrow(s, m.d_values, n, &d_packed, &bits);
     if (!stp.ok()) return stp;
     m.d_packed = d_packed.release();
-    m.d_packed_pages = d_packed_pages.release();
     if (bits) {
       m.packed_bits = bits;
       hipFree(m.d_values);  // the 8-byte words are not needed any more
@@ -522,9 +505,9 @@ Status table_rt_column(evql_table* t, const std::string& name, RtColumn* out,
     out->tags = m.d_tags;
     if (strpos) *strpos = m.d_strpos;
     if (m.packed_bits) {
-      c.mode = ColAccess::BITPACKED;
+      c.mode = ColAccess::NARROW;
       out->bits = m.packed_bits;
-      out->pages = m.d_packed_pages;
+      out->pages = nullptr;
       out->base = m.d_packed;
     }
   }

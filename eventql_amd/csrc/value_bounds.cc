@@ -91,7 +91,7 @@ Status column_abs_max(evql_query* q, size_t i, double* out) {
     n = q->nested_rows;
   } else if (c.packed) {
     const MaterializedColumn& m = t->materialized[c.name];
-    rc.pages = m.d_packed_pages;
+    rc.pages = nullptr;  // (a flat array: ColAccess::NARROW)
     rc.base = m.d_packed;
   } else if (c.mode == ColAccess::SOA) {
     rc.soa = t->materialized[c.name].d_values;

@@ -33,9 +33,9 @@ Status table_zone_map(evql_table* t, const std::string& name, const evql_table::
     // a PLAIN column the table keeps a narrow copy of is read from the copy
     auto m = t->materialized.find(name);
     if (m != t->materialized.end() && m->second.packed_bits) {
-      rc.mode = uint32_t(ColAccess::BITPACKED);
+      rc.mode = uint32_t(ColAccess::NARROW);
       rc.bits = m->second.packed_bits;
-      rc.pages = m->second.d_packed_pages;
+      rc.pages = nullptr;
       rc.base = m->second.d_packed;
     }
   }

@@ -856,7 +856,10 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch,
 /* Compile the fused kernel of `plan` for gfx950 without a device (used by
  * __graft_entry__.build() and the CPU test-suite).  Stores the code object in
  * the on-disk kernel cache when cache_dir != NULL.  Plans of one shape (see
- * evql_query_create) give one code object. */
+ * evql_query_create) give one code object.  Widths are not known without pages:
+ * columns[i].payload_bytes carries the bit width of a bit-packed column; on a required
+ * UINT64_PLAIN / UINT64_LEB128 column, 8 / 16 / 32 there selects the shape that reads the
+ * flat narrow copy a resident table keeps of it. */
 int evql_compile_only(const evql_plan_desc_t* plan,
                       const evql_column_info_t* columns, int ncolumns,
                       const char* cache_dir, size_t* code_size);
