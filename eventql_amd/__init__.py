@@ -548,7 +548,9 @@ class LsmChain:
         return np.unpackbits(raw, bitorder="little")[:n.value].astype(bool), kept.value
 
     def query(self, plan):
-        """the operator over the whole chain (GroupByExpression over PartitionCursor)"""
+        """the operator over the whole chain (GroupByExpression over PartitionCursor); after
+        execute() it can be exchanged with the other ranks' operators (Query.exchange) like a
+        query over a single table"""
         q = C.c_void_p()
         _check(lib().evql_query_create_chain(self.ctx.h, self.h, C.byref(plan.desc), C.byref(q)))
         return Query(self, plan, q)

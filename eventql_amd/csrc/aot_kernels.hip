@@ -61,6 +61,54 @@ __global__ void k_table_compact(const u64* words, u64 gcap, u64 stride, u32 nwor
   }
 }
 
+// k_table_compact over the merged table of a chain head on its way into an exchange: a slot
+// with its kind word in front IS a wire record (first-row words resolved, strings as heap
+// offsets), only the scan position gets the rank in front of (table << 44 | row).  Words move
+// four at a time through registers (fixed trip count: nothing is indexed by a lane), and
+// consecutive lanes write consecutive records.
+__global__ void __launch_bounds__(kBlock) k_mtab_compact(const u64* __restrict__ words, u64 gcap,
+                                                         u32 nwords, u32 pos_word, u64 rank_tag,
+                                                         u64* __restrict__ out, u64 max_records,
+                                                         u64* counter) {
+  __shared__ u64 base_s;  // one atomic per workgroup and round, as in k_table_compact
+  const u64 nslots = gcap + 2;
+  const u64 step = (u64) gridDim.x * blockDim.x;
+  const u64 rounds = (nslots + step - 1) / step;
+  for (u64 it = 0; it < rounds; ++it) {
+    const u64 s = (it * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+    const u64* slot = words + s * nwords;
+    const u64 k = s < nslots ? slot[0] : EVQL_EMPTY;
+    const bool occ = k != EVQL_EMPTY;
+    u32 total;
+    const u32 ex = block_excl_scan(occ ? 1u : 0u, &total);
+    if (threadIdx.x == 0) base_s = total ? atomicAdd(counter, (u64) total) : 0;
+    __syncthreads();
+    const u64 idx = base_s + ex;
+    __syncthreads();
+    if (!occ || idx >= max_records) continue;
+    u64* rec = out + idx * (nwords + 1);
+    rec[0] = s == gcap ? 1ull : (s == gcap + 1 ? 2ull : 0ull);
+    rec[1] = s == gcap ? EVQL_EMPTY : k;
+    u32 w = 1;
+    for (; w + 4 <= nwords; w += 4) {
+      u64 v[4];
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) v[j] = slot[w + j];
+#pragma unroll
+      for (u32 j = 0; j < 4; ++j) {
+        // (an unrecorded position stays the largest one)
+        if (w + j == pos_word && v[j] != EVQL_EMPTY) v[j] |= rank_tag;
+        rec[1 + w + j] = v[j];
+      }
+    }
+    for (; w < nwords; ++w) {
+      u64 v = slot[w];
+      if (w == pos_word && v != EVQL_EMPTY) v |= rank_tag;
+      rec[1 + w] = v;
+    }
+  }
+}
+
 // number of occupied slots (count-only form of the compaction)
 __global__ void __launch_bounds__(kBlock) k_table_count(const u64* words, u64 gcap, u32 nwords,
                                                         u64* counter) {
@@ -429,7 +477,11 @@ __global__ void __launch_bounds__(kBlock) k_wire_str_copy(WireStrArgs a) {
       const u64 sp = rec[a.word[k]];
       const u64 off = sp & kStrOffMask;
       const u32 len = (u32) (sp >> 40);
-      for (u32 b = 0; b < len; ++b) a.heap[pos + b] = vbyte_fwd(a.image, (const u64*) a.pages[k], off + b);
+      if (a.flat) {
+        for (u32 b = 0; b < len; ++b) a.heap[pos + b] = a.flat[off + b];
+      } else {
+        for (u32 b = 0; b < len; ++b) a.heap[pos + b] = vbyte_fwd(a.image, (const u64*) a.pages[k], off + b);
+      }
       rec[a.word[k]] = ((u64) len << 40) | (pos - seg0);
       pos += len;
     }
@@ -2299,6 +2351,16 @@ hipError_t launch_table_compact(const uint64_t* words, uint64_t gcap, uint64_t s
   hipLaunchKernelGGL(k_table_compact, dim3(grid_for(gcap + 2)), dim3(kBlock), 0, s,
                      (const u64*) words, (u64) gcap, (u64) stride, nwords, (u64*) out_records,
                      (u64) max_records, (u64*) counter);
+  return hipGetLastError();
+}
+
+hipError_t launch_mtab_compact(const uint64_t* words, uint64_t gcap, uint32_t nwords,
+                               uint32_t pos_word, uint64_t rank_tag, uint64_t* out_records,
+                               uint64_t max_records, uint64_t* counter, hipStream_t s) {
+  if (max_records == 0 || nwords == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mtab_compact, dim3(grid_for(gcap + 2)), dim3(kBlock), 0, s,
+                     (const u64*) words, (u64) gcap, nwords, pos_word, (u64) rank_tag,
+                     (u64*) out_records, (u64) max_records, (u64*) counter);
   return hipGetLastError();
 }
 

@@ -97,8 +97,9 @@ namespace {
 
 // Every rank reaches every barrier of a collective even after a local failure (a rank
 // that returned early would leave its peers waiting on the condition variable for
-// ever); the first error is kept in the hub and every rank reports it.  An exchange
-// error is fatal to the hub / communicator: the caller tears it down.
+// ever); the first error is kept in the hub and every rank reports it.  A transport
+// error is fatal to the hub / communicator: the caller tears it down.  (A refusal that
+// exchange() agrees on in its go / no-go gather is none: it never comes through here.)
 int hub_fail(evql_hub* h, int code, const char* msg) {
   std::unique_lock<std::mutex> lk(h->mu);
   if (h->error == EVQL_OK) {
@@ -232,24 +233,26 @@ static const uint32_t kMergeSkip = 254;  // (rt_atomic knows no such op: the wor
 // stored triples of pair set `which` go to the ranks that own their groups (all ranks
 // for GATHER_ALL) and are inserted into a fresh set there; every triple that is new to
 // it adds 1 to state word `word` of its group in the merged table.
+// `src_set` / `src_cap`: this rank's own set -- the scan's, or for a chain head the chain's
+// merged one, which is also the destination: its triples are in the workspace before it is
+// reallocated or cleared.
 static Status exchange_pairset(evql_query* q, evql_exchange* x, bool by_owner, int which,
-                               uint32_t word, uint64_t mcap, uint32_t mw) {
+                               const uint64_t* src_set, uint64_t src_cap, uint32_t word,
+                               uint64_t mcap, uint32_t mw) {
   hipStream_t s = q->ctx->stream;
   const int N = x->nranks;
   const bool exact = q->kp.key_mode == KEY_EXACT;
   uint64_t np = 0;
   uint64_t* d_cnt = q->d_counters + 6;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-  if (q->d_pairset[which]) {
-    HIP_TRY(launch_pairset_export(q->d_pairset[which], q->pairset_cap, nullptr, 0, d_cnt, s));
-  }
+  if (src_set) HIP_TRY(launch_pairset_export(src_set, src_cap, nullptr, 0, d_cnt, s));
   HIP_TRY(hipMemcpyAsync(&np, d_cnt, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   WsBuf<uint64_t> d_tr(x, 11), d_send(x, 12), d_aux(x, 4), d_recv(x, 13);
   HIP_TRY(d_tr.alloc(std::max<uint64_t>(np, 1) * 24));
   if (np) {
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-    HIP_TRY(launch_pairset_export(q->d_pairset[which], q->pairset_cap, d_tr, np, d_cnt, s));
+    HIP_TRY(launch_pairset_export(src_set, src_cap, d_tr, np, d_cnt, s));
   }
   std::vector<uint64_t> send_counts(N, np), starts(N + 1, 0);
   const uint64_t* d_out = d_tr;
@@ -458,38 +461,95 @@ static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolve
 // -----------------------------------------------------------------------------------------
 // the exchange itself
 // -----------------------------------------------------------------------------------------
-Status exchange(evql_query* q, evql_exchange* x, int mode) {
+// *source_gone: set once the call starts to overwrite what it reads its groups from (only a
+// chain head's: d_mtab / d_mset are source and destination)
+static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* source_gone) {
   evql_ctx* ctx = q->ctx;
   evql_table* t = q->table;
   hipStream_t s = ctx->stream;
   const KernelPlan& kp = q->rplan();
   const int N = x->nranks;
-  if (!q->executed) return Status::error(EVQL_EARG, "execute() was not called");
   if (N > int(kMaxExchangeRanks)) return Status::error(EVQL_EARG, "too many ranks");
-  if (q->merged) return Status::error(EVQL_EARG, "the query was exchanged already");
+  // a chain head (evql_query_create_chain over two or more files): its groups are the ones
+  // chain_merge left in d_mtab
+  const bool from_chain = q->merged && q->chain_merged;
   const uint32_t W = uint32_t(kp.words_per_slot());
   const uint32_t nc = uint32_t(kp.cols.size());
   const bool resolved = kp.need_first_row;
   const uint32_t rw_in = W + 1;
   const uint32_t rw = resolved ? rw_in + nc + 1 : rw_in;  // wire record words
-  // (checked before anything is allocated or filled: the merged slot is W + nc + 1 words)
-  if ((resolved ? W + nc + 1 : W) > uint32_t(kMaxStateWords + 3)) {
-    return Status::error(EVQL_ENOTSUP, "too many words per merged group");
+  uint64_t str_mask = 0;
+  std::vector<uint32_t> str_cols;
+  for (uint32_t c = 0; resolved && c < nc; ++c) {
+    if (kp.cols[c].string_hash) {
+      str_mask |= 1ull << c;
+      str_cols.push_back(c);
+    }
   }
   auto t0 = std::chrono::steady_clock::now();
   x->stats = evql_exchange_stats_t{};
+
+  // ---- 0. go / no-go --------------------------------------------------------------------------
+  // What this rank alone can tell -- before anything is allocated or filled (the merged slot
+  // is W + nc + 1 words) -- only sets a status: a rank that returned here would leave its
+  // peers waiting in the first collective.  One gather of [status, tables scanned, the four
+  // exact-sum quanta] per rank tells everybody; a refusal is no transport error and leaves
+  // the hub / communicator as it was.
+  Status pre;
+  if (!q->executed) {
+    pre = Status::error(EVQL_EARG, "execute() was not called");
+  } else if (q->merged && !q->chain_merged) {
+    pre = Status::error(EVQL_EARG, "the query was exchanged already");
+  } else if ((resolved ? W + nc + 1 : W) > uint32_t(kMaxStateWords + 3)) {
+    pre = Status::error(EVQL_ENOTSUP, "too many words per merged group");
+  } else if (str_cols.size() > kMaxWireStrCols) {
+    pre = Status::error(EVQL_ENOTSUP, "too many string columns in an exchanged plan");
+  } else if (from_chain && q->m_words + 1 != rw) {
+    pre = Status::error(EVQL_ERUNTIME, "chain: the merged slots do not match the plan");
+  }
+  const uint32_t kGo = 6;
+  std::vector<uint64_t> mine_g(kGo), all_g(uint64_t(kGo) * N);
+  mine_g[0] = uint64_t(int64_t(pre.code));
+  mine_g[1] = 1 + q->chain.size();
+  for (int k = 0; k < 4; ++k) mine_g[2 + k] = uint64_t(int64_t(q->fsum_exp[k]));
+  {
+    int rcg = x->tr.all_gather_u64(x->tr.user, mine_g.data(), kGo, all_g.data());
+    if (rcg != EVQL_OK) return Status::error(rcg, "exchange: all_gather of the go / no-go records failed");
+  }
+  if (!pre.ok()) return pre;
+  uint64_t max_tables = 1;
+  for (int r = 0; r < N; ++r) {
+    const int code = int(int64_t(all_g[uint64_t(r) * kGo]));
+    if (code != EVQL_OK) {
+      return Status::error(EVQL_ERUNTIME, "exchange refused by rank " + std::to_string(r) +
+                                              " (status " + std::to_string(code) + ")");
+    }
+    max_tables = std::max(max_tables, all_g[uint64_t(r) * kGo + 1]);
+  }
+  // the scan position of a first row, ordered by (rank, table of the chain, row):
+  // rank << (44 + tb) | table << 44 | row.  No chain anywhere: tb = 0, rank << 44 | row.
+  auto bits_of = [](uint64_t v) {
+    uint32_t b = 0;
+    while (v) {
+      ++b;
+      v >>= 1;
+    }
+    return b;
+  };
+  const uint32_t tb = bits_of(max_tables - 1);
+  if (resolved && 44 + tb + bits_of(uint64_t(N - 1)) > 63) {
+    // (every rank sees the same counts: all of them answer this)
+    return Status::error(EVQL_ENOTSUP, "too many ranks x tables of a chain for the scan position word");
+  }
+  const uint64_t rank_tag = uint64_t(x->rank) << (44 + tb);
   if (kp.n_exact > 0) {
     // EVQL_FLOAT_SUM_EXACT: the state words are integer multiples of 2^fsum_exp and are
     // added as they are -- every rank must have chosen the same quantum.  With
     // float_sum_bound = 0 each rank derives it from its OWN table's maxima, which may
     // fall on either side of a power of two.
-    std::vector<uint64_t> mine_e(4), all_e(uint64_t(4) * N);
-    for (int k = 0; k < 4; ++k) mine_e[k] = uint64_t(int64_t(q->fsum_exp[k]));
-    int rce = x->tr.all_gather_u64(x->tr.user, mine_e.data(), 4, all_e.data());
-    if (rce != EVQL_OK) return Status::error(rce, "exchange: all_gather of the sum quanta failed");
     for (int r = 0; r < N; ++r) {
       for (int k = 0; k < kp.n_exact; ++k) {
-        if (all_e[uint64_t(r) * 4 + k] != mine_e[k]) {
+        if (all_g[uint64_t(r) * kGo + 2 + k] != mine_g[2 + k]) {
           return Status::error(EVQL_EARG,
                                "exact float sums: the ranks chose different quanta (the tables' "
                                "maxima differ); pass the same float_sum_bound on every rank");
@@ -499,10 +559,24 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
   }
 
   // ---- 1. this rank's groups as dense records ---------------------------------------------
-  const uint64_t n = q->ngroups;
+  // (a chain head: the count chain_merge left, which a fetch under ORDER BY .. LIMIT keeps
+  // -- q->ngroups is then the number of rows that fetch emitted)
+  const uint64_t n = from_chain ? q->stats.num_groups : q->ngroups;
   WsBuf<uint64_t> d_rec(x, 0);
   const uint64_t* d_records = nullptr;  // n records of rw_in words
-  {
+  WsBuf<uint64_t> d_wire(x, 1);
+  if (from_chain) {
+    // a slot of the merged table behind its kind word is a wire record already (first-row
+    // words resolved inside the table that produced them, strings as offsets into the
+    // chain's heap): steps 1 and 2 are one pass, which also puts the rank in front of the
+    // scan position.  It is complete on the stream before step 6 re-initialises d_mtab.
+    HIP_TRY(d_wire.alloc(std::max<uint64_t>(n, 1) * rw * 8));
+    uint64_t* d_cnt = q->d_counters + 6;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+    HIP_TRY(launch_mtab_compact(q->d_mtab, q->mcap, q->m_words,
+                                resolved ? uint32_t(kp.first_row_word()) : 0xffffffffu, rank_tag,
+                                d_wire, n, d_cnt, s));
+  } else {
     RecordsView view;
     Status stv = query_records_view(q, &view);
     if (!stv.ok()) return stv;
@@ -523,10 +597,7 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
     }
   }
   // ---- 2. first-row values into the records (plans that need them) -------------------------
-  WsBuf<uint64_t> d_wire(x, 1);
-  uint64_t str_mask = 0;
-  std::vector<uint32_t> str_cols;
-  if (resolved) {
+  if (resolved && !from_chain) {
     std::vector<RtColumn> rc(nc);
     for (uint32_t c = 0; c < nc; ++c) {
       const ColAccess& ca = kp.cols[c];
@@ -546,13 +617,6 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
         rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
         rc[c].tags = m.d_tags;
       }
-      if (ca.string_hash) {
-        str_mask |= 1ull << c;
-        str_cols.push_back(c);
-      }
-    }
-    if (str_cols.size() > kMaxWireStrCols) {
-      return Status::error(EVQL_ENOTSUP, "too many string columns in an exchanged plan");
     }
     WsBuf<RtColumn> d_cols(x, 2);
     HIP_TRY(d_cols.alloc(std::max<uint32_t>(nc, 1) * sizeof(RtColumn)));
@@ -564,14 +628,14 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
     ra.ncols = nc;
     ra.in_words = rw_in;
     ra.first_row_word = uint32_t(1 + kp.first_row_word());
-    ra.rank_tag = uint64_t(x->rank) << 44;
+    ra.rank_tag = rank_tag;
     ra.in = d_records;
     ra.n = n;
     ra.out = d_wire;
     HIP_TRY(launch_resolve_records(ra, s));
     HIP_TRY(hipStreamSynchronize(s));  // (d_cols / rc live until here)
   }
-  const uint64_t* d_src = resolved ? d_wire.p : d_records;
+  const uint64_t* d_src = resolved || from_chain ? d_wire.p : d_records;
 
   // ---- 3. bucket by owner ---------------------------------------------------------------------
   std::vector<uint64_t> send_counts(N, 0), starts(N + 1, 0);
@@ -620,7 +684,15 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
     for (size_t k = 0; k < str_cols.size(); ++k) {
       wa.word[k] = rw_in + str_cols[k];
       wa.col[k] = str_cols[k];
-      wa.pages[k] = t->d_pages[kp.cols[str_cols[k]].layout_index][0];
+      if (!from_chain) wa.pages[k] = t->d_pages[kp.cols[str_cols[k]].layout_index][0];
+    }
+    if (from_chain) {
+      // (the chain's first-row strings: offsets into its device heap)
+      if (!q->d_mheap.p) {  // (every string empty)
+        HIP_TRY(q->d_mheap.alloc(8));
+        q->mheap_cap = 8;
+      }
+      wa.flat = q->d_mheap;
     }
     HIP_TRY(d_sizes.alloc((n + 2) * 8));
     wa.sizes = d_sizes;
@@ -742,6 +814,7 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
   }
 
   // ---- 6. merge, one batch per source rank, in rank order, into a fresh table --------------------
+  *source_gone = from_chain;
   const uint32_t mw = resolved ? W + nc + 1 : W;  // slot words of the merged table
   TableInitArgs ia{};
   ia.nwords = mw;
@@ -827,7 +900,9 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
   // ---- 7. count_distinct: the pair sets follow their groups --------------------------------------
   for (const auto& ag : kp.aggs) {
     if (ag.distinct_index < 0) continue;
-    Status st = exchange_pairset(q, x, by_owner, ag.distinct_index,
+    const int d = ag.distinct_index;
+    Status st = exchange_pairset(q, x, by_owner, d, from_chain ? q->d_mset[d] : q->d_pairset[d],
+                                 from_chain ? q->mset_cap[d] : q->pairset_cap,
                                  uint32_t(kp.state_word_base() + ag.first_word), cap, mw);
     if (!st.ok()) return st;
   }
@@ -843,12 +918,31 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
     HIP_TRY(hipMemcpy(q->m_heap.data(), d_hrecv, total_heap_words * 8, hipMemcpyDeviceToHost));
   }
   q->merged = true;
+  q->chain_merged = false;  // (d_mtab / d_mdense now hold the exchanged groups)
   q->ngroups = ng;
   q->stats.num_groups = ng;
   q->fetched = false;
   q->emit_pos = 0;
   x->stats.merge_ms = ms_since(t2);
   return Status();
+}
+
+Status exchange(evql_query* q, evql_exchange* x, int mode) {
+  bool source_gone = false;
+  Status st = exchange_steps(q, x, mode, &source_gone);
+  if (!st.ok() && source_gone) {
+    // A late failure (merged table / set full, a transport error behind step 5) of a chain
+    // head: its merged table and sets are re-initialised or half filled with exchanged data.
+    // A plain query still has d_gtab; this one holds nothing it could emit or exchange again
+    // and asks for a new execute().
+    q->executed = false;
+    q->merged = false;
+    q->chain_merged = false;
+    q->merged_dense = false;
+    q->ngroups = 0;
+    q->stats.num_groups = 0;
+  }
+  return st;
 }
 
 }  // namespace
@@ -1058,6 +1152,18 @@ Status chain_merge(evql_query* head) {
     HIP_TRY(hipStreamSynchronize(s));  // (rc / seg live until here)
     if (heap_bytes) {
       const size_t old = head->m_heap.size();
+      // the same bytes stay on the device: an exchange of this head exports them from there
+      if (old + heap_bytes > head->mheap_cap) {
+        const uint64_t want = std::max<uint64_t>(2 * head->mheap_cap, old + heap_bytes + 4096);
+        DevBuf<uint8_t> grown;
+        HIP_TRY(grown.alloc(want));
+        if (old) HIP_TRY(hipMemcpyAsync(grown, head->d_mheap, old, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        head->d_mheap = std::move(grown);
+        head->mheap_cap = want;
+      }
+      HIP_TRY(hipMemcpyAsync(head->d_mheap.p + old, d_heap, heap_bytes, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipStreamSynchronize(s));  // (d_heap is allocated anew for the next table)
       head->m_heap.resize(old + heap_bytes);
       HIP_TRY(hipMemcpy(head->m_heap.data() + old, d_heap, heap_bytes, hipMemcpyDeviceToHost));
     }
@@ -1135,6 +1241,7 @@ Status chain_merge(evql_query* head) {
   if (status[0] & 2u) return Status::error(EVQL_ENOMEM, "merged group table full");
   if (status[0] & 8u) return Status::error(EVQL_ENOMEM, "merged count_distinct set full");
   head->merged = true;
+  head->chain_merged = true;
   head->ngroups = ng;
   head->stats.num_groups = ng;
   head->stats.rows_scanned = rows_scanned;

@@ -452,6 +452,7 @@ Status query_launch(evql_query* q) {
   }
   q->probed = true;
   q->merged = false;
+  q->chain_merged = false;
   q->merged_dense = false;
   q->conv_valid = false;
   const KernelPlan& kp = q->kp;
@@ -933,6 +934,7 @@ Status query_reset(evql_query* q) {
   q->ngroups = 0;
   q->dense_n = 0;
   q->merged = false;
+  q->chain_merged = false;
   q->merged_dense = false;
   q->stats.num_groups = 0;
   q->stats.rows_scanned = 0;

@@ -314,6 +314,12 @@ struct evql_query {
   uint64_t mcap = 0;
   uint32_t m_words = 0;
   std::vector<uint8_t> m_heap;  // received string bytes
+  // `merged` by chain_merge and not (yet) by an exchange: d_mtab holds this partition's own
+  // groups, which evql_query_exchange takes as its source (instead of d_gtab); the string
+  // words of its slots point into m_heap, kept once more on the device for that export
+  bool chain_merged = false;
+  evql::DevBuf<uint8_t> d_mheap;
+  uint64_t mheap_cap = 0;  // bytes allocated; m_heap.size() of them are filled
   // large merges (exchange.cc bucketed_merge) leave dense records [kind, slot words...]
   // instead of a table
   bool merged_dense = false;

@@ -719,6 +719,26 @@ typedef enum {
  * value) pairs follow their groups and are counted again in the merged set
  * (aggregate.cc:119-137), also for EVQL_MODE_PARTIAL plans (their rows then carry the
  * merged sets' values).
+ *
+ * The head of a chain (evql_query_create_chain over two or more files) is accepted like a
+ * plain query: its source is the table the chain's files were merged into, compacted into
+ * wire records in one pass on the device, its first-row strings and count_distinct pairs
+ * come from the chain's own merged heap and sets.  Ranks over chains and ranks over single
+ * tables may be mixed.  First rows are then ordered by rank, inside a rank by file in scan
+ * order, inside a file by row: one position word rank << (44 + tb) | file << 44 | row,
+ * where tb is the bit count of (the largest number of files of any rank) - 1 -- with no
+ * chain anywhere tb = 0.  Plans that read first-row values are refused with EVQL_ENOTSUP
+ * on every rank when 44 + tb + bits(nranks - 1) exceeds 63.
+ *
+ * Go / no-go: the call starts with ONE all_gather_u64 of a 6-word record per rank (status,
+ * number of files, the four exact-sum quanta).  What a rank can only tell by itself --
+ * execute() was not called, the query was exchanged already (a second exchange needs an
+ * execute() in between), too many words or string columns per merged group -- travels in
+ * it: that rank returns its own code and message, every other rank EVQL_ERUNTIME "exchange
+ * refused by rank <r> (status <code>)", nobody enters a further collective, the query keeps
+ * its result, and the hub / communicator stays usable.  Errors of the transport itself are
+ * still fatal to it.  A chain head whose exchange fails after its merged table was
+ * re-initialised holds no result any more: it wants a new execute().
  */
 int evql_query_exchange(evql_query_t* q, evql_exchange_t* x, int mode);
 
