@@ -863,7 +863,7 @@ int evql_query_export_groups(evql_query_t* q, void* device_dst, uint64_t max_gro
   }
   hipStream_t s = q->ctx->stream;
   if (!q->d_gtab || !q->d_counters) return fail(EVQL_EARG, "execute() was not called");
-  uint64_t* d_cnt = q->d_counters + 6;  // per-query counter block: no allocation per call
+  uint64_t* d_cnt = q->d_counters + kScratchCounter;  // per-query counter block: no allocation per call
   const uint32_t nwords = uint32_t(q->kp.words_per_slot());
   // (partitioned path) the dense records as they are, the table's groups behind them
   const uint64_t nd = q->dense_n;
@@ -908,17 +908,9 @@ int evql_query_import_groups(evql_query_t* q, const void* device_src, uint64_t n
   a.words = q->d_gtab;
   a.gcap = q->gcap;
   a.stride = q->gcap + 8;
-  a.nwords = uint32_t(q->kp.words_per_slot());
-  int w = 1;
-  a.has_ident2 = q->kp.has_ident2() ? 1 : 0;
-  if (q->kp.has_ident2()) a.ops[w++] = 255;
-  if (q->kp.need_first_row) a.ops[w++] = 2;  // min
-  for (const auto& sw : q->kp.states) a.ops[w++] = uint32_t(sw.op);
   // a count_distinct word counts the pairs of THIS query's set: foreign counts are not
-  // added, the pairs arrive through evql_query_import_pairs and are counted there
-  for (const auto& ag : q->kp.aggs) {
-    if (ag.distinct_index >= 0) a.ops[q->kp.state_word_base() + ag.first_word] = 254;  // no such op: skipped
-  }
+  // added (kMergeSkip), the pairs arrive through evql_query_import_pairs and are counted there
+  merge_ops(q->kp, true, &a);
   a.status = q->d_status;
   hipMemsetAsync(q->d_status, 0, 16, s);
   hipError_t e = launch_table_merge(a, static_cast<const uint64_t*>(device_src), n_groups, s);
@@ -951,7 +943,7 @@ int evql_query_export_pairs(evql_query_t* q, uint32_t which, void* device_dst, u
   hipStream_t s = q->ctx->stream;
   *n_pairs = 0;
   if (!q->d_pairset[which]) return EVQL_OK;  // (nothing scanned yet: an empty merge target)
-  uint64_t* d_cnt = q->d_counters + 6;
+  uint64_t* d_cnt = q->d_counters + kScratchCounter;
   hipMemsetAsync(d_cnt, 0, 8, s);
   hipError_t e = launch_pairset_export(q->d_pairset[which], q->pairset_cap,
                                        static_cast<uint64_t*>(device_dst), device_dst ? max_pairs : 0,

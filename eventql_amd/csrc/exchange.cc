@@ -227,7 +227,53 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-static const uint32_t kMergeSkip = 254;  // (rt_atomic knows no such op: the word is left alone)
+// One exchange: what crosses its steps, and the steps in the order exchange_steps runs them.
+struct ExchangeRun {
+  evql_query* const q;
+  evql_exchange* const x;
+  const hipStream_t s;
+  const int N;
+  const GroupRecordLayout L;
+  // a chain head (a chain of two or more files): its groups are those chain_merge left in d_mtab
+  const bool from_chain;
+  const bool by_owner;    // else: every rank gets every record
+  uint64_t n = 0, rank_tag = 0;  // this rank's groups; what goes in front of their scan positions
+  // device buffers: slots of the exchange's workspace
+  WsBuf<uint64_t> d_rec{x, 0}, d_wire{x, 1}, d_send{x, 3}, d_aux{x, 4}, d_sizes{x, 5}, d_recv{x, 7},
+      d_rep{x, 8}, d_hsend{x, 9}, d_hrecv{x, 10};
+  WsBuf<RtColumn> d_cols{x, 2};
+  WsBuf<uint8_t> d_heap{x, 6};
+  // this rank's n wire records, what is sent, the received records rank by rank
+  const uint64_t *d_src = nullptr, *d_out = nullptr, *d_in = nullptr;
+  std::vector<uint64_t> send_counts, starts;  // records per owner, first record of every owner
+  std::vector<uint64_t> heap_counts;          // string bytes per destination
+  std::vector<uint64_t> recv_rec, hbase;      // per source rank: records, first byte of its strings
+  uint64_t total_rec = 0, total_heap_words = 0;
+  uint64_t ng = 0;  // merged groups (read back by finish_merge's synchronisation)
+  std::chrono::steady_clock::time_point t0, t1, t2;
+
+  ExchangeRun(evql_query* qq, evql_exchange* xx, int mode)
+      : q(qq), x(xx), s(qq->ctx->stream), N(xx->nranks), L(group_record_layout(qq->rplan())),
+        from_chain(qq->merged && qq->chain_merged),
+        by_owner(mode == EVQL_EXCHANGE_BY_OWNER && xx->nranks > 1), send_counts(N, 0),
+        starts(N + 1, 0), heap_counts(N, 0), recv_rec(N, 0), hbase(N, 0) {}
+  // d_aux: [counts per owner | starts | cursors]
+  static constexpr size_t kAuxBytes = (3 * kMaxExchangeRanks + 4) * 8;
+  uint64_t* d_counts() const { return d_aux.p; }
+  uint64_t* d_starts() const { return d_aux.p + kMaxExchangeRanks; }
+  uint64_t* d_cursors() const { return d_aux.p + 2 * kMaxExchangeRanks + 2; }
+
+  Status go_no_go();
+  Status export_records();
+  Status bucket_by_owner();
+  Status export_strings();
+  Status transfer();
+  Status merge_received();
+  Status bucketed_merge(bool* done);
+  Status exchange_pairsets();
+  Status exchange_pairset(int which, const uint64_t* src_set, uint64_t src_cap, uint32_t word);
+  Status finish_merge();
+};
 
 // count_distinct (aggregate.cc:77-137: a std::set per group, merged by insertion): the
 // stored triples of pair set `which` go to the ranks that own their groups (all ranks
@@ -236,61 +282,49 @@ static const uint32_t kMergeSkip = 254;  // (rt_atomic knows no such op: the wor
 // `src_set` / `src_cap`: this rank's own set -- the scan's, or for a chain head the chain's
 // merged one, which is also the destination: its triples are in the workspace before it is
 // reallocated or cleared.
-static Status exchange_pairset(evql_query* q, evql_exchange* x, bool by_owner, int which,
-                               const uint64_t* src_set, uint64_t src_cap, uint32_t word,
-                               uint64_t mcap, uint32_t mw) {
-  hipStream_t s = q->ctx->stream;
-  const int N = x->nranks;
+Status ExchangeRun::exchange_pairset(int which, const uint64_t* src_set, uint64_t src_cap,
+                               uint32_t word) {
   const bool exact = q->kp.key_mode == KEY_EXACT;
   uint64_t np = 0;
-  uint64_t* d_cnt = q->d_counters + 6;
-  HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-  if (src_set) HIP_TRY(launch_pairset_export(src_set, src_cap, nullptr, 0, d_cnt, s));
-  HIP_TRY(hipMemcpyAsync(&np, d_cnt, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  WsBuf<uint64_t> d_tr(x, 11), d_send(x, 12), d_aux(x, 4), d_recv(x, 13);
+  uint64_t* d_cnt = q->d_counters + kScratchCounter;
+  Status st = pairset_count(q, src_set, src_cap, &np);
+  if (!st.ok()) return st;
+  WsBuf<uint64_t> d_tr(x, 11), d_tsend(x, 12), d_trecv(x, 13);
   HIP_TRY(d_tr.alloc(std::max<uint64_t>(np, 1) * 24));
   if (np) {
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
     HIP_TRY(launch_pairset_export(src_set, src_cap, d_tr, np, d_cnt, s));
   }
-  std::vector<uint64_t> send_counts(N, np), starts(N + 1, 0);
-  const uint64_t* d_out = d_tr;
+  std::vector<uint64_t> tr_counts(N, np), tr_starts(N + 1, 0);
   if (by_owner) {
-    HIP_TRY(d_send.alloc(std::max<uint64_t>(np, 1) * 24));
-    HIP_TRY(d_aux.alloc((3 * kMaxExchangeRanks + 4) * 8));
-    uint64_t* d_counts = d_aux.p;
-    uint64_t* d_starts = d_aux.p + kMaxExchangeRanks;
-    uint64_t* d_cursors = d_aux.p + 2 * kMaxExchangeRanks + 2;
-    HIP_TRY(hipMemsetAsync(d_aux, 0, (3 * kMaxExchangeRanks + 4) * 8, s));
-    HIP_TRY(launch_triple_owner_hist(d_tr, np, uint32_t(N), exact, d_counts, s));
-    HIP_TRY(hipMemcpyAsync(send_counts.data(), d_counts, N * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(d_tsend.alloc(std::max<uint64_t>(np, 1) * 24));
+    HIP_TRY(hipMemsetAsync(d_aux, 0, kAuxBytes, s));  // (bucket_by_owner's)
+    HIP_TRY(launch_triple_owner_hist(d_tr, np, uint32_t(N), exact, d_counts(), s));
+    HIP_TRY(hipMemcpyAsync(tr_counts.data(), d_counts(), N * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (int r = 0; r < N; ++r) starts[r + 1] = starts[r] + send_counts[r];
-    HIP_TRY(hipMemcpyAsync(d_starts, starts.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_triple_owner_scatter(d_tr, np, uint32_t(N), exact, d_starts, d_cursors, d_send, s));
-    d_out = d_send;
+    for (int r = 0; r < N; ++r) tr_starts[r + 1] = tr_starts[r] + tr_counts[r];
+    HIP_TRY(hipMemcpyAsync(d_starts(), tr_starts.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_triple_owner_scatter(d_tr, np, uint32_t(N), exact, d_starts(), d_cursors(), d_tsend, s));
   } else {
     // the same triples to everybody (replicated per destination like the records)
-    HIP_TRY(d_send.alloc(std::max<uint64_t>(np * N, 1) * 24));
+    HIP_TRY(d_tsend.alloc(std::max<uint64_t>(np * N, 1) * 24));
     for (int r = 0; r < N; ++r) {
-      HIP_TRY(hipMemcpyAsync(d_send.p + uint64_t(r) * np * 3, d_tr, np * 24, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d_tsend.p + uint64_t(r) * np * 3, d_tr, np * 24, hipMemcpyDeviceToDevice, s));
     }
-    d_out = d_send;
   }
   std::vector<uint64_t> all(uint64_t(N) * N);
-  int rc = x->tr.all_gather_u64(x->tr.user, send_counts.data(), N, all.data());
+  int rc = x->tr.all_gather_u64(x->tr.user, tr_counts.data(), N, all.data());
   if (rc != EVQL_OK) return Status::error(rc, "exchange: all_gather of the pair counts failed");
   std::vector<uint64_t> send_words(N), recv_words(N);
   uint64_t total = 0;
   for (int r = 0; r < N; ++r) {
     const uint64_t from_r = all[uint64_t(r) * N + x->rank];
-    send_words[r] = send_counts[r] * 3;
+    send_words[r] = tr_counts[r] * 3;
     recv_words[r] = from_r * 3;
     total += from_r;
   }
-  HIP_TRY(d_recv.alloc(std::max<uint64_t>(total, 1) * 24));
-  rc = x->tr.all_to_all_words(x->tr.user, d_out, send_words.data(), d_recv, recv_words.data(), s);
+  HIP_TRY(d_trecv.alloc(std::max<uint64_t>(total, 1) * 24));
+  rc = x->tr.all_to_all_words(x->tr.user, d_tsend, send_words.data(), d_trecv, recv_words.data(), s);
   if (rc != EVQL_OK) return Status::error(rc, "exchange: transfer of the count_distinct pairs failed");
   HIP_TRY(hipStreamSynchronize(s));
   x->stats.bytes_sent += (by_owner ? np : np * uint64_t(N - 1)) * 24;
@@ -298,27 +332,7 @@ static Status exchange_pairset(evql_query* q, evql_exchange* x, bool by_owner, i
   while (set_cap < total * 2) set_cap <<= 1;
   // the merged set belongs to the query: EVQL_MODE_PARTIAL rows carry the values of every
   // group's set (aggregate.cc:111-117), read back from here at emission
-  if (q->d_mset[which] && q->mset_cap[which] != set_cap) {
-    hipFree(q->d_mset[which]);
-    q->d_mset[which] = nullptr;
-  }
-  if (!q->d_mset[which]) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_mset[which]), set_cap * 24));
-  }
-  q->mset_cap[which] = set_cap;
-  uint64_t* d_set = q->d_mset[which];
-  HIP_TRY(hipMemsetAsync(d_set, 0xff, set_cap * 24, s));
-  PairsetMergeArgs pa{};
-  pa.set = d_set;
-  pa.set_cap = set_cap;
-  pa.words = q->d_mtab;
-  pa.gcap = mcap;
-  pa.nwords = mw;
-  pa.word = word;
-  pa.key_mode = uint32_t(q->kp.key_mode);
-  pa.status = q->d_status;
-  HIP_TRY(launch_pairset_merge(pa, d_recv, total, s));
-  return Status();
+  return merged_set_fill(q, L, which, set_cap, word, d_trecv, total);
 }
 
 // -----------------------------------------------------------------------------------------
@@ -333,13 +347,9 @@ static Status exchange_pairset(evql_query* q, evql_exchange* x, bool by_owner, i
 // tile / an LDS table) or a region outgrew its slack -- the caller merges through the table.
 static const uint64_t kBucketedMergeMin = 1ull << 18;
 
-static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolvedArgs& ma,
-                             const uint64_t* identity, const uint64_t* d_recv,
-                             const std::vector<uint64_t>& recv_rec,
-                             const std::vector<uint64_t>& hbase, uint64_t total_rec, bool* done) {
+Status ExchangeRun::bucketed_merge(bool* done) {
   *done = false;
-  hipStream_t s = q->ctx->stream;
-  const uint32_t mw = ma.m.nwords, rw = mw + 1;
+  const uint32_t mw = L.mw, rw = mw + 1;
   if (total_rec < kBucketedMergeMin || recv_rec.size() > kMaxExchangeRanks) return Status();
   // LDS table of a bucket: <= 60 KB (30 KB tables = twice the buckets measured slower: 1.44 vs
   // 1.05 ms per 1e7 records), power of two slots + the two keyless groups
@@ -385,7 +395,7 @@ static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolve
     q->mdense_cap = total_rec;
   }
   BucketScatterArgs sa{};
-  sa.in = d_recv;
+  sa.in = d_in;
   sa.out = d_stage1;
   sa.in_counts = nullptr;
   sa.n_in = total_rec;
@@ -400,9 +410,9 @@ static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolve
   sa.out_region_cap = cap1;
   sa.out_counts = d_cnt1;
   sa.status = d_flag;
-  sa.first_value_word = 1 + ma.state_words;
-  sa.ncols = ma.ncols;
-  sa.str_mask = ma.str_mask;
+  sa.first_value_word = 1 + L.W;
+  sa.ncols = L.nc;
+  sa.str_mask = L.str_mask;
   sa.nranks = uint32_t(recv_rec.size());
   uint64_t off = 0;
   for (size_t r = 0; r < recv_rec.size(); ++r) {
@@ -433,15 +443,15 @@ static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolve
   ba.region_cap = two_levels ? cap2 : cap1;
   ba.buckets = uint32_t(F);
   ba.mw = mw;
-  ba.has_ident2 = ma.m.has_ident2;
-  ba.state_words = ma.state_words;
-  ba.first_row_word = ma.first_row_word;
-  ba.ncols = ma.first_row_word == 0xffffffffu ? 0 : ma.ncols;
+  ba.has_ident2 = L.has_ident2;
+  ba.state_words = L.W;
+  ba.first_row_word = L.first_row_word;
+  ba.ncols = L.resolved ? L.nc : 0;
   ba.lds_slots = slots;
-  for (uint32_t w = 0; w < mw; ++w) {
-    ba.ops[w] = ma.m.ops[w];
-    ba.identity[w] = identity[w];
-  }
+  MergeArgs m{};
+  merge_ops(q->rplan(), true, &m);
+  for (uint32_t w = 0; w < mw; ++w) ba.ops[w] = m.ops[w];
+  slot_identities(q->rplan(), mw, ba.identity);
   ba.out = q->d_mdense;
   ba.out_cap = q->mdense_cap;
   ba.out_count = d_out_count;
@@ -459,52 +469,20 @@ static Status bucketed_merge(evql_query* q, evql_exchange* x, const MergeResolve
 }
 
 // -----------------------------------------------------------------------------------------
-// the exchange itself
+// the exchange itself: its steps in the order exchange_steps runs them
 // -----------------------------------------------------------------------------------------
-// *source_gone: set once the call starts to overwrite what it reads its groups from (only a
-// chain head's: d_mtab / d_mset are source and destination)
-static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* source_gone) {
-  evql_ctx* ctx = q->ctx;
-  evql_table* t = q->table;
-  hipStream_t s = ctx->stream;
+// What this rank alone can tell -- before anything is allocated or filled -- only sets a
+// status: a rank that returned here would leave its peers waiting in the first collective.
+// One gather of [status, tables scanned, the four exact-sum quanta] per rank tells
+// everybody; a refusal is no transport error and leaves the hub / communicator as it was.
+Status ExchangeRun::go_no_go() {
   const KernelPlan& kp = q->rplan();
-  const int N = x->nranks;
-  if (N > int(kMaxExchangeRanks)) return Status::error(EVQL_EARG, "too many ranks");
-  // a chain head (evql_query_create_chain over two or more files): its groups are the ones
-  // chain_merge left in d_mtab
-  const bool from_chain = q->merged && q->chain_merged;
-  const uint32_t W = uint32_t(kp.words_per_slot());
-  const uint32_t nc = uint32_t(kp.cols.size());
-  const bool resolved = kp.need_first_row;
-  const uint32_t rw_in = W + 1;
-  const uint32_t rw = resolved ? rw_in + nc + 1 : rw_in;  // wire record words
-  uint64_t str_mask = 0;
-  std::vector<uint32_t> str_cols;
-  for (uint32_t c = 0; resolved && c < nc; ++c) {
-    if (kp.cols[c].string_hash) {
-      str_mask |= 1ull << c;
-      str_cols.push_back(c);
-    }
-  }
-  auto t0 = std::chrono::steady_clock::now();
-  x->stats = evql_exchange_stats_t{};
-
-  // ---- 0. go / no-go --------------------------------------------------------------------------
-  // What this rank alone can tell -- before anything is allocated or filled (the merged slot
-  // is W + nc + 1 words) -- only sets a status: a rank that returned here would leave its
-  // peers waiting in the first collective.  One gather of [status, tables scanned, the four
-  // exact-sum quanta] per rank tells everybody; a refusal is no transport error and leaves
-  // the hub / communicator as it was.
-  Status pre;
+  Status pre = group_record_layout_check(L, "an exchanged");
   if (!q->executed) {
     pre = Status::error(EVQL_EARG, "execute() was not called");
   } else if (q->merged && !q->chain_merged) {
     pre = Status::error(EVQL_EARG, "the query was exchanged already");
-  } else if ((resolved ? W + nc + 1 : W) > uint32_t(kMaxStateWords + 3)) {
-    pre = Status::error(EVQL_ENOTSUP, "too many words per merged group");
-  } else if (str_cols.size() > kMaxWireStrCols) {
-    pre = Status::error(EVQL_ENOTSUP, "too many string columns in an exchanged plan");
-  } else if (from_chain && q->m_words + 1 != rw) {
+  } else if (pre.ok() && from_chain && q->m_words + 1 != L.rw) {
     pre = Status::error(EVQL_ERUNTIME, "chain: the merged slots do not match the plan");
   }
   const uint32_t kGo = 6;
@@ -512,10 +490,8 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   mine_g[0] = uint64_t(int64_t(pre.code));
   mine_g[1] = 1 + q->chain.size();
   for (int k = 0; k < 4; ++k) mine_g[2 + k] = uint64_t(int64_t(q->fsum_exp[k]));
-  {
-    int rcg = x->tr.all_gather_u64(x->tr.user, mine_g.data(), kGo, all_g.data());
-    if (rcg != EVQL_OK) return Status::error(rcg, "exchange: all_gather of the go / no-go records failed");
-  }
+  const int rcg = x->tr.all_gather_u64(x->tr.user, mine_g.data(), kGo, all_g.data());
+  if (rcg != EVQL_OK) return Status::error(rcg, "exchange: all_gather of the go / no-go records failed");
   if (!pre.ok()) return pre;
   uint64_t max_tables = 1;
   for (int r = 0; r < N; ++r) {
@@ -530,18 +506,15 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   // rank << (44 + tb) | table << 44 | row.  No chain anywhere: tb = 0, rank << 44 | row.
   auto bits_of = [](uint64_t v) {
     uint32_t b = 0;
-    while (v) {
-      ++b;
-      v >>= 1;
-    }
+    for (; v; v >>= 1) ++b;
     return b;
   };
   const uint32_t tb = bits_of(max_tables - 1);
-  if (resolved && 44 + tb + bits_of(uint64_t(N - 1)) > 63) {
+  if (L.resolved && 44 + tb + bits_of(uint64_t(N - 1)) > 63) {
     // (every rank sees the same counts: all of them answer this)
     return Status::error(EVQL_ENOTSUP, "too many ranks x tables of a chain for the scan position word");
   }
-  const uint64_t rank_tag = uint64_t(x->rank) << (44 + tb);
+  rank_tag = uint64_t(x->rank) << (44 + tb);
   if (kp.n_exact > 0) {
     // EVQL_FLOAT_SUM_EXACT: the state words are integer multiples of 2^fsum_exp and are
     // added as they are -- every rank must have chosen the same quantum.  With
@@ -557,181 +530,106 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
       }
     }
   }
+  return Status();
+}
 
-  // ---- 1. this rank's groups as dense records ---------------------------------------------
-  // (a chain head: the count chain_merge left, which a fetch under ORDER BY .. LIMIT keeps
+// This rank's groups as wire records (d_src): dense records, with first-row values if resolved.
+Status ExchangeRun::export_records() {
+  // (a chain head: the count the chain merge left, which a fetch under ORDER BY .. LIMIT keeps
   // -- q->ngroups is then the number of rows that fetch emitted)
-  const uint64_t n = from_chain ? q->stats.num_groups : q->ngroups;
-  WsBuf<uint64_t> d_rec(x, 0);
-  const uint64_t* d_records = nullptr;  // n records of rw_in words
-  WsBuf<uint64_t> d_wire(x, 1);
+  n = from_chain ? q->stats.num_groups : q->ngroups;
   if (from_chain) {
     // a slot of the merged table behind its kind word is a wire record already (first-row
     // words resolved inside the table that produced them, strings as offsets into the
-    // chain's heap): steps 1 and 2 are one pass, which also puts the rank in front of the
-    // scan position.  It is complete on the stream before step 6 re-initialises d_mtab.
-    HIP_TRY(d_wire.alloc(std::max<uint64_t>(n, 1) * rw * 8));
-    uint64_t* d_cnt = q->d_counters + 6;
+    // chain's heap): one pass, which also puts the rank in front of the scan position.  It
+    // is complete on the stream before merge_received re-initialises d_mtab.
+    HIP_TRY(d_wire.alloc(std::max<uint64_t>(n, 1) * L.rw * 8));
+    uint64_t* d_cnt = q->d_counters + kScratchCounter;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-    HIP_TRY(launch_mtab_compact(q->d_mtab, q->mcap, q->m_words,
-                                resolved ? uint32_t(kp.first_row_word()) : 0xffffffffu, rank_tag,
+    HIP_TRY(launch_mtab_compact(q->d_mtab, q->mcap, q->m_words, L.first_row_word, rank_tag,
                                 d_wire, n, d_cnt, s));
-  } else {
-    RecordsView view;
-    Status stv = query_records_view(q, &view);
-    if (!stv.ok()) return stv;
-    const uint64_t nd = view.nd;
-    if (n && nd == n) {
-      // (the partitioned path left every group as a dense record: read in place)
-      d_records = view.dense;
-    } else {
-      HIP_TRY(d_rec.alloc(std::max<uint64_t>(n, 1) * rw_in * 8));
-      if (nd) HIP_TRY(hipMemcpyAsync(d_rec, view.dense, nd * rw_in * 8, hipMemcpyDeviceToDevice, s));
-      if (n > nd) {
-        uint64_t* d_cnt = q->d_counters + 6;
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-        HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, W, d_rec.p + nd * rw_in, n - nd,
-                                     d_cnt, s));
-      }
-      d_records = d_rec;
-    }
+    d_src = d_wire;
+    return Status();
   }
-  // ---- 2. first-row values into the records (plans that need them) -------------------------
-  if (resolved && !from_chain) {
-    std::vector<RtColumn> rc(nc);
-    for (uint32_t c = 0; c < nc; ++c) {
-      const ColAccess& ca = kp.cols[c];
-      rc[c] = RtColumn{};
-      rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
-      rc[c].mode = ca.mode;
-      rc[c].bits = ca.bits;
-      if (q->nested) {
-        rc[c].mode = ColAccess::SOA;  // (the 8-byte words stay beside a packed copy)
-        rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
-      } else if (ca.packed) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
-        rc[c].base = m.d_packed;
-      } else if (ca.mode == ColAccess::SOA) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
-        rc[c].tags = m.d_tags;
-      }
-    }
-    WsBuf<RtColumn> d_cols(x, 2);
-    HIP_TRY(d_cols.alloc(std::max<uint32_t>(nc, 1) * sizeof(RtColumn)));
-    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-    HIP_TRY(d_wire.alloc(std::max<uint64_t>(n, 1) * rw * 8));
-    ResolveArgs ra{};
-    ra.image = t->d_image;
-    ra.cols = d_cols;
-    ra.ncols = nc;
-    ra.in_words = rw_in;
-    ra.first_row_word = uint32_t(1 + kp.first_row_word());
-    ra.rank_tag = rank_tag;
-    ra.in = d_records;
-    ra.n = n;
-    ra.out = d_wire;
-    HIP_TRY(launch_resolve_records(ra, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (d_cols / rc live until here)
+  RecordsView view;
+  Status st = query_records_view(q, &view);
+  if (!st.ok()) return st;
+  const uint64_t* d_records = view.dense;  // n records of rw_in words
+  if (!(n && view.nd == n)) {
+    // (else the partitioned path left every group as a dense record: read in place)
+    HIP_TRY(d_rec.alloc(std::max<uint64_t>(n, 1) * L.rw_in * 8));
+    st = query_dense_records(q, L, view, d_rec);
+    if (!st.ok()) return st;
+    d_records = d_rec;
   }
-  const uint64_t* d_src = resolved || from_chain ? d_wire.p : d_records;
+  d_src = d_records;
+  if (!L.resolved) return Status();
+  HIP_TRY(d_cols.alloc(std::max<uint32_t>(L.nc, 1) * sizeof(RtColumn)));
+  HIP_TRY(d_wire.alloc(std::max<uint64_t>(n, 1) * L.rw * 8));
+  std::vector<RtColumn> rc;
+  st = resolve_first_rows(q, L, rank_tag, &rc, d_cols, d_records, n, d_wire);
+  if (!st.ok()) return st;
+  HIP_TRY(hipStreamSynchronize(s));  // (d_cols / rc live until here)
+  d_src = d_wire;
+  return Status();
+}
 
-  // ---- 3. bucket by owner ---------------------------------------------------------------------
-  std::vector<uint64_t> send_counts(N, 0), starts(N + 1, 0);
-  WsBuf<uint64_t> d_send(x, 3), d_aux(x, 4);
+// The wire records in the order they are sent (d_out), send_counts / starts.
+Status ExchangeRun::bucket_by_owner() {
+  const uint32_t rw = L.rw;
   HIP_TRY(d_send.alloc(std::max<uint64_t>(n, 1) * rw * 8));
-  const uint64_t* d_out = d_send.p;  // what is sent
-  HIP_TRY(d_aux.alloc((3 * kMaxExchangeRanks + 4) * 8));
-  uint64_t* d_counts = d_aux.p;
-  uint64_t* d_starts = d_aux.p + kMaxExchangeRanks;
-  uint64_t* d_cursors = d_aux.p + 2 * kMaxExchangeRanks + 2;
-  if (mode == EVQL_EXCHANGE_BY_OWNER && N > 1) {
-    HIP_TRY(hipMemsetAsync(d_aux, 0, (3 * kMaxExchangeRanks + 4) * 8, s));
-    HIP_TRY(launch_owner_hist(d_src, n, rw, uint32_t(N), d_counts, s));
-    HIP_TRY(hipMemcpyAsync(send_counts.data(), d_counts, N * 8, hipMemcpyDeviceToHost, s));
+  d_out = d_send.p;
+  HIP_TRY(d_aux.alloc(kAuxBytes));
+  if (by_owner) {
+    HIP_TRY(hipMemsetAsync(d_aux, 0, kAuxBytes, s));
+    HIP_TRY(launch_owner_hist(d_src, n, rw, uint32_t(N), d_counts(), s));
+    HIP_TRY(hipMemcpyAsync(send_counts.data(), d_counts(), N * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int r = 0; r < N; ++r) starts[r + 1] = starts[r] + send_counts[r];
-    HIP_TRY(hipMemcpyAsync(d_starts, starts.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_owner_scatter(d_src, n, rw, uint32_t(N), d_starts, d_cursors, d_send, s));
+    HIP_TRY(hipMemcpyAsync(d_starts(), starts.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_owner_scatter(d_src, n, rw, uint32_t(N), d_starts(), d_cursors(), d_send, s));
+    return Status();
+  }
+  // every rank gets every record: "bucket" r = all of them (copied only when the string
+  // words are about to be rewritten in place, export_strings)
+  if (!L.str_cols.empty()) {
+    HIP_TRY(hipMemcpyAsync(d_send, d_src, n * rw * 8, hipMemcpyDeviceToDevice, s));
   } else {
-    // every rank gets every record: "bucket" r = all of them (copied only when the string
-    // words are about to be rewritten in place, step 4)
-    if (resolved && !str_cols.empty()) {
-      HIP_TRY(hipMemcpyAsync(d_send, d_src, n * rw * 8, hipMemcpyDeviceToDevice, s));
-    } else {
-      d_out = d_src;
-    }
-    for (int r = 0; r < N; ++r) send_counts[r] = n;
-    starts[0] = 0;
-    for (int r = 1; r <= N; ++r) starts[r] = n;  // (one segment)
+    d_out = d_src;
   }
-  const bool by_owner = mode == EVQL_EXCHANGE_BY_OWNER && N > 1;
+  for (int r = 0; r < N; ++r) send_counts[r] = n;
+  for (int r = 1; r <= N; ++r) starts[r] = n;  // (one segment)
+  return Status();
+}
 
-  // ---- 4. string bytes of the records, in record order ------------------------------------------
-  WsBuf<uint64_t> d_sizes(x, 5);
-  WsBuf<uint8_t> d_heap(x, 6);
-  std::vector<uint64_t> heap_counts(N, 0);  // bytes per destination (padded to words)
-  uint64_t heap_bytes = 0;
-  if (resolved && !str_cols.empty() && n) {
-    WireStrArgs wa{};
-    wa.image = t->d_image;
-    wa.records = d_send;
-    wa.n = n;
-    wa.rw = rw;
-    wa.tags_word = rw_in + nc;
-    wa.nstr = uint32_t(str_cols.size());
-    for (size_t k = 0; k < str_cols.size(); ++k) {
-      wa.word[k] = rw_in + str_cols[k];
-      wa.col[k] = str_cols[k];
-      if (!from_chain) wa.pages[k] = t->d_pages[kp.cols[str_cols[k]].layout_index][0];
+// String bytes in record order: d_heap, heap_counts (transfer re-packs them to whole words).
+Status ExchangeRun::export_strings() {
+  if (L.str_cols.empty() || !n) return Status();
+  const uint8_t* flat = nullptr;
+  if (from_chain) {
+    // (the chain's first-row strings: offsets into its device heap)
+    if (!q->d_mheap.p) {  // (every string empty)
+      HIP_TRY(q->d_mheap.alloc(8));
+      q->mheap_cap = 8;
     }
-    if (from_chain) {
-      // (the chain's first-row strings: offsets into its device heap)
-      if (!q->d_mheap.p) {  // (every string empty)
-        HIP_TRY(q->d_mheap.alloc(8));
-        q->mheap_cap = 8;
-      }
-      wa.flat = q->d_mheap;
-    }
-    HIP_TRY(d_sizes.alloc((n + 2) * 8));
-    wa.sizes = d_sizes;
-    wa.nranks = by_owner ? uint32_t(N) : 1u;
-    std::vector<uint64_t> seg(N + 1, 0);
-    if (by_owner) {
-      seg = starts;
-    } else {
-      seg[1] = n;
-    }
-    HIP_TRY(hipMemcpyAsync(d_starts, seg.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
-    wa.starts = d_starts;
-    HIP_TRY(launch_wire_str_sizes(wa, s));
-    HIP_TRY(launch_exclusive_scan(d_sizes, n, d_sizes.p + n, s));
-    HIP_TRY(hipMemcpyAsync(&heap_bytes, d_sizes.p + n, 8, hipMemcpyDeviceToHost, s));
-    // segment borders in bytes
-    std::vector<uint64_t> segoff(N + 1, 0);
-    HIP_TRY(hipStreamSynchronize(s));
-    const int nseg = by_owner ? N : 1;
-    for (int r = 1; r <= nseg; ++r) {
-      if (seg[r] >= n) {
-        segoff[r] = heap_bytes;
-      } else {
-        HIP_TRY(hipMemcpy(&segoff[r], d_sizes.p + seg[r], 8, hipMemcpyDeviceToHost));
-      }
-    }
-    HIP_TRY(d_heap.alloc(heap_bytes + 8 * (N + 1)));
-    wa.heap = d_heap;
-    HIP_TRY(launch_wire_str_copy(wa, s));
-    for (int r = 0; r < N; ++r) {
-      heap_counts[r] = by_owner ? segoff[r + 1] - segoff[r] : heap_bytes;
-    }
-    // (segments are sent as whole words: their starts have to be 8-aligned -- they are
-    // re-packed below)
+    flat = q->d_mheap;
   }
-  x->stats.export_ms = ms_since(t0);
-  auto t1 = std::chrono::steady_clock::now();
+  HIP_TRY(d_sizes.alloc((n + 2) * 8));
+  const uint32_t nseg = by_owner ? uint32_t(N) : 1u;  // (GATHER_ALL: starts = [0, n, ..], one segment)
+  std::vector<uint64_t> segoff(N + 1, 0);
+  auto heap_for = [&](uint64_t bytes) {
+    return d_heap.alloc(bytes + 8 * (N + 1)) == hipSuccess ? d_heap.p : nullptr;
+  };
+  Status st = wire_strings(q, L, flat, d_send, n, starts.data(), nseg, d_sizes, d_starts(), heap_for,
+                           segoff.data());
+  if (!st.ok()) return st;
+  for (int r = 0; r < N; ++r) heap_counts[r] = by_owner ? segoff[r + 1] - segoff[r] : segoff[1];
+  return Status();
+}
 
-  // ---- 5. counts, then the records (and the string bytes) --------------------------------------
+// Counts, then the records and the string bytes: d_in / recv_rec, d_hrecv / hbase.
+Status ExchangeRun::transfer() {
+  const uint32_t rw = L.rw;
   // per destination: [record count, heap bytes]
   std::vector<uint64_t> mine(2 * N), all(uint64_t(2) * N * N);
   for (int r = 0; r < N; ++r) {
@@ -740,8 +638,7 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   }
   int rc = x->tr.all_gather_u64(x->tr.user, mine.data(), 2 * N, all.data());
   if (rc != EVQL_OK) return Status::error(rc, "exchange: all_gather of the counts failed");
-  std::vector<uint64_t> recv_rec(N), recv_heap(N), send_words(N), recv_words(N);
-  uint64_t total_rec = 0, total_heap_words = 0;
+  std::vector<uint64_t> recv_heap(N), send_words(N), recv_words(N);
   for (int r = 0; r < N; ++r) {
     recv_rec[r] = all[uint64_t(r) * 2 * N + 2 * x->rank];
     recv_heap[r] = all[uint64_t(r) * 2 * N + 2 * x->rank + 1];
@@ -750,9 +647,8 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
     send_words[r] = mine[2 * r] * rw;
     recv_words[r] = recv_rec[r] * rw;
   }
-  WsBuf<uint64_t> d_recv(x, 7);
   HIP_TRY(d_recv.alloc(std::max<uint64_t>(N == 1 ? 1 : total_rec, 1) * rw * 8));
-  const uint64_t* d_in = d_recv.p;  // the received records, rank by rank
+  d_in = d_recv.p;
   if (by_owner) {
     rc = x->tr.all_to_all_words(x->tr.user, d_send, send_words.data(), d_recv, recv_words.data(), s);
   } else {
@@ -763,7 +659,6 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
       // a single rank receives exactly what it sends: merged where it lies
       d_in = d_out;
     } else {
-      WsBuf<uint64_t> d_rep(x, 8);
       HIP_TRY(d_rep.alloc(std::max<uint64_t>(n * rw * N, 1) * 8));
       for (int r = 0; r < N; ++r) {
         HIP_TRY(hipMemcpyAsync(d_rep.p + uint64_t(r) * n * rw, d_out, n * rw * 8,
@@ -775,9 +670,7 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   }
   if (rc != EVQL_OK) return Status::error(rc, "exchange: transfer of the records failed");
   // string heaps: word-aligned segments
-  WsBuf<uint64_t> d_hsend(x, 9), d_hrecv(x, 10);
-  std::vector<uint64_t> hbase(N, 0);
-  if (resolved && !str_cols.empty()) {
+  if (!L.str_cols.empty()) {
     std::vector<uint64_t> hs(N), hr(N);
     uint64_t tot = 0;
     for (int r = 0; r < N; ++r) {
@@ -806,114 +699,70 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   }
   HIP_TRY(hipStreamSynchronize(s));
   x->stats.transfer_ms = ms_since(t1);
-  auto t2 = std::chrono::steady_clock::now();
+  t2 = std::chrono::steady_clock::now();
   x->stats.groups_sent = by_owner ? n : n * uint64_t(N);
   x->stats.groups_received = total_rec;
   for (int r = 0; r < N; ++r) {
     if (r != x->rank) x->stats.bytes_sent += send_words[r] * 8 + heap_counts[r];
   }
+  return Status();
+}
 
-  // ---- 6. merge, one batch per source rank, in rank order, into a fresh table --------------------
-  *source_gone = from_chain;
-  const uint32_t mw = resolved ? W + nc + 1 : W;  // slot words of the merged table
-  TableInitArgs ia{};
-  ia.nwords = mw;
-  ia.identity[0] = 0xFFFFFFFFFFFFFFFFull;
-  int w = 1;
-  if (kp.has_ident2()) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  if (kp.need_first_row) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  static const uint64_t kIdent[8] = {0, 0, 0xFFFFFFFFFFFFFFFFull, 0, 0x7FFFFFFFFFFFFFFFull,
-                                     0x8000000000000000ull, 0x7FF0000000000000ull,
-                                     0xFFF0000000000000ull};
-  for (const auto& sw : kp.states) ia.identity[w++] = kIdent[sw.op & 7];
-  for (; w < int(mw); ++w) ia.identity[w] = 0;
-  MergeResolvedArgs ma{};
-  ma.m.nwords = mw;
-  ma.m.has_ident2 = kp.has_ident2() ? 1 : 0;
-  w = 1;
-  if (kp.has_ident2()) ma.m.ops[w++] = 255;
-  if (kp.need_first_row) ma.m.ops[w++] = 2;
-  for (const auto& sw : kp.states) ma.m.ops[w++] = uint32_t(sw.op);
-  // a count_distinct word counts the pairs of the MERGED set: foreign counts are not
-  // added, the pairs are exchanged below and counted again
-  bool has_distinct = false;
-  for (const auto& ag : kp.aggs) {
-    if (ag.distinct_index >= 0) {
-      ma.m.ops[kp.state_word_base() + ag.first_word] = kMergeSkip;
-      has_distinct = true;
-    }
-  }
-  ma.m.status = q->d_status;
-  ma.state_words = W;
-  ma.first_row_word = resolved ? uint32_t(kp.first_row_word()) : 0xffffffffu;
-  ma.ncols = nc;
-  ma.str_mask = str_mask;
+// The received records into a fresh table -- or, when they are many, into dense records.
+Status ExchangeRun::merge_received() {
   HIP_TRY(hipMemsetAsync(q->d_status, 0, 16, s));
   q->merged_dense = false;
-  uint64_t ng = 0;
-  uint64_t cap = 0;
   bool bucketed = false;
-  if (!has_distinct) {
-    Status stb = bucketed_merge(q, x, ma, ia.identity, d_in, recv_rec, hbase, total_rec, &bucketed);
+  if (q->rplan().n_distinct == 0) {
+    Status stb = bucketed_merge(&bucketed);
     if (!stb.ok()) return stb;
   }
   if (bucketed) {
     ng = q->mdense_n;
-    q->m_words = mw;
-  } else {
-    cap = 1 << 16;
-    while (cap < total_rec * 2) cap <<= 1;
-    if (!q->d_mtab || q->mcap != cap || q->m_words != mw) {
-      if (q->d_mtab) hipFree(q->d_mtab);
-      q->d_mtab = nullptr;
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q->d_mtab), (cap + 8) * uint64_t(mw) * 8));
-    }
-    q->mcap = cap;
-    q->m_words = mw;
-    ia.words = q->d_mtab;
-    ia.stride = cap + 8;
-    HIP_TRY(launch_table_init(ia, s));
-    ma.m.words = q->d_mtab;
-    ma.m.gcap = cap;
-    ma.m.stride = cap + 8;
-    // the records of one source rank are its groups: pairwise different identities, one
-    // launch per rank -- plain read-modify-write behind the identity CAS, new slots counted
-    // as they are claimed
-    uint64_t* d_ngroups = q->d_counters + 4;
-    ma.m.exclusive = 1;
-    ma.m.fresh = d_ngroups;
-    HIP_TRY(hipMemsetAsync(d_ngroups, 0, 8, s));
-    uint64_t roff = 0;
-    for (int r = 0; r < N; ++r) {
-      if (recv_rec[r]) {
-        if (resolved) {
-          ma.heap_base = hbase[r];
-          HIP_TRY(launch_table_merge_resolved(ma, d_in + roff * rw, recv_rec[r], s));
-        } else {
-          HIP_TRY(launch_table_merge(ma.m, d_in + roff * rw, recv_rec[r], s));
-        }
-      }
-      roff += recv_rec[r];
-    }
-    HIP_TRY(hipMemcpyAsync(&ng, d_ngroups, 8, hipMemcpyDeviceToHost, s));
+    q->m_words = L.mw;
+    return Status();
   }
-  // ---- 7. count_distinct: the pair sets follow their groups --------------------------------------
+  MergeResolvedArgs ma;
+  Status st = merged_table_prepare(q, L, total_rec, &ma);
+  if (!st.ok()) return st;
+  uint64_t roff = 0;
+  for (int r = 0; r < N; ++r) {  // (one launch per source rank, in rank order)
+    ma.heap_base = hbase[r];
+    if (recv_rec[r] && L.resolved) {
+      HIP_TRY(launch_table_merge_resolved(ma, d_in + roff * L.rw, recv_rec[r], s));
+    } else if (recv_rec[r]) {
+      HIP_TRY(launch_table_merge(ma.m, d_in + roff * L.rw, recv_rec[r], s));
+    }
+    roff += recv_rec[r];
+  }
+  HIP_TRY(hipMemcpyAsync(&ng, ma.m.fresh, 8, hipMemcpyDeviceToHost, s));
+  return Status();
+}
+
+// count_distinct: the pair sets follow their groups
+Status ExchangeRun::exchange_pairsets() {
+  const KernelPlan& kp = q->rplan();
   for (const auto& ag : kp.aggs) {
     if (ag.distinct_index < 0) continue;
     const int d = ag.distinct_index;
-    Status st = exchange_pairset(q, x, by_owner, d, from_chain ? q->d_mset[d] : q->d_pairset[d],
+    Status st = exchange_pairset(d, from_chain ? q->d_mset[d] : q->d_pairset[d],
                                  from_chain ? q->mset_cap[d] : q->pairset_cap,
-                                 uint32_t(kp.state_word_base() + ag.first_word), cap, mw);
+                                 uint32_t(kp.state_word_base() + ag.first_word));
     if (!st.ok()) return st;
   }
+  return Status();
+}
+
+// what the merge kernels reported, then the query holds the exchanged groups
+Status ExchangeRun::finish_merge() {
   uint32_t status[4] = {0};
   HIP_TRY(hipMemcpyAsync(status, q->d_status, 16, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (status[0] & 2u) return Status::error(EVQL_ENOMEM, "merged group table full");
-  if (status[0] & 8u) return Status::error(EVQL_ENOMEM, "merged count_distinct set full");
+  Status st = merge_status_error(status[0], "merged ");
+  if (!st.ok()) return st;
   // the received string bytes are what the merged groups' string words point into
   q->m_heap.clear();
-  if (resolved && !str_cols.empty() && total_heap_words) {
+  if (!L.str_cols.empty() && total_heap_words) {
     q->m_heap.resize(total_heap_words * 8);
     HIP_TRY(hipMemcpy(q->m_heap.data(), d_hrecv, total_heap_words * 8, hipMemcpyDeviceToHost));
   }
@@ -927,14 +776,37 @@ static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* so
   return Status();
 }
 
+// *source_gone: set once the call starts to overwrite what it reads its groups from (only a
+// chain head's: d_mtab / d_mset are source and destination)
+static Status exchange_steps(evql_query* q, evql_exchange* x, int mode, bool* source_gone) {
+  if (x->nranks > int(kMaxExchangeRanks)) return Status::error(EVQL_EARG, "too many ranks");
+  ExchangeRun R(q, x, mode);
+  R.t0 = std::chrono::steady_clock::now();
+  x->stats = evql_exchange_stats_t{};
+  Status st = R.go_no_go();  // (the first collective: no rank returns before it)
+  if (st.ok()) st = R.export_records();
+  if (st.ok()) st = R.bucket_by_owner();
+  if (st.ok()) st = R.export_strings();
+  if (!st.ok()) return st;
+  x->stats.export_ms = ms_since(R.t0);
+  R.t1 = std::chrono::steady_clock::now();
+  st = R.transfer();
+  if (!st.ok()) return st;
+  *source_gone = R.from_chain;
+  st = R.merge_received();
+  if (st.ok()) st = R.exchange_pairsets();
+  if (st.ok()) st = R.finish_merge();
+  return st;
+}
+
 Status exchange(evql_query* q, evql_exchange* x, int mode) {
   bool source_gone = false;
   Status st = exchange_steps(q, x, mode, &source_gone);
   if (!st.ok() && source_gone) {
-    // A late failure (merged table / set full, a transport error behind step 5) of a chain
-    // head: its merged table and sets are re-initialised or half filled with exchanged data.
-    // A plain query still has d_gtab; this one holds nothing it could emit or exchange again
-    // and asks for a new execute().
+    // A late failure (merged table / set full, a transport error behind the transfer) of a
+    // chain head: its merged table and sets are re-initialised or half filled with exchanged
+    // data.  A plain query still has d_gtab; this one holds nothing it could emit or exchange
+    // again and asks for a new execute().
     q->executed = false;
     q->merged = false;
     q->chain_merged = false;
@@ -946,314 +818,6 @@ Status exchange(evql_query* q, evql_exchange* x, int mode) {
 }
 
 }  // namespace
-
-// -----------------------------------------------------------------------------------------
-// chains: the tables of one partition scanned by one operator each (evql_query_create_chain)
-// -----------------------------------------------------------------------------------------
-// PartitionCursor hands the batches of its scans to ONE GroupByExpression, newest table
-// first (server/sql/partition_cursor.cc:56-81, groupby.cc:69-185).  Here every table was
-// aggregated by its own launch; their groups are merged like the partial aggregates of
-// several ranks -- table i plays rank i: records in chain order into a fresh table, first
-// rows resolved inside the table that produced them, (table << 44 | row) as the scan
-// position, string bytes into one heap, count_distinct pairs re-inserted into one set.
-namespace evql {
-
-Status chain_merge(evql_query* head) {
-  evql_ctx* ctx = head->ctx;
-  hipStream_t s = ctx->stream;
-  const KernelPlan& kp = head->rplan();
-  std::vector<evql_query*> parts;
-  parts.push_back(head);
-  for (evql_query* c : head->chain) parts.push_back(c);
-  const uint32_t W = uint32_t(kp.words_per_slot());
-  const uint32_t nc = uint32_t(kp.cols.size());
-  const bool resolved = kp.need_first_row;
-  const uint32_t rw_in = W + 1;
-  const uint32_t rw = resolved ? rw_in + nc + 1 : rw_in;
-  const uint32_t mw = resolved ? W + nc + 1 : W;
-  if (mw > uint32_t(kMaxStateWords + 3)) {
-    return Status::error(EVQL_ENOTSUP, "too many words per merged group");
-  }
-  if (parts.size() >= (1u << 19)) return Status::error(EVQL_EARG, "too many tables in a chain");
-  uint64_t total = 0, max_n = 0;
-  for (evql_query* p : parts) {
-    // (same plan everywhere: the slot layouts agree; a different KEY mode or word count
-    // would mean different plans)
-    // (a table whose string key has no usable dictionary keeps the hashed plan; its
-    // records have the same rplan() layout as the coded tables')
-    if (uint32_t(p->rplan().words_per_slot()) != W || p->rplan().cols.size() != nc ||
-        p->rplan().key_mode != kp.key_mode || p->rplan().need_first_row != kp.need_first_row) {
-      return Status::error(EVQL_ERUNTIME, "chain: the tables' plans disagree");
-    }
-    if (!p->executed) return Status::error(EVQL_EARG, "execute() was not called");
-    total += p->ngroups;
-    max_n = std::max(max_n, p->ngroups);
-  }
-  // ---- the merged table ---------------------------------------------------------------------
-  uint64_t cap = 1 << 16;
-  while (cap < total * 2) cap <<= 1;
-  if (!head->d_mtab || head->mcap != cap || head->m_words != mw) {
-    if (head->d_mtab) hipFree(head->d_mtab);
-    head->d_mtab = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&head->d_mtab), (cap + 8) * uint64_t(mw) * 8));
-  }
-  head->mcap = cap;
-  head->m_words = mw;
-  TableInitArgs ia{};
-  ia.words = head->d_mtab;
-  ia.stride = cap + 8;
-  ia.nwords = mw;
-  ia.identity[0] = 0xFFFFFFFFFFFFFFFFull;
-  int w = 1;
-  if (kp.has_ident2()) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  if (kp.need_first_row) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  static const uint64_t kIdent[8] = {0, 0, 0xFFFFFFFFFFFFFFFFull, 0, 0x7FFFFFFFFFFFFFFFull,
-                                     0x8000000000000000ull, 0x7FF0000000000000ull,
-                                     0xFFF0000000000000ull};
-  for (const auto& sw : kp.states) ia.identity[w++] = kIdent[sw.op & 7];
-  for (; w < int(mw); ++w) ia.identity[w] = 0;
-  HIP_TRY(launch_table_init(ia, s));
-  MergeResolvedArgs ma{};
-  ma.m.words = head->d_mtab;
-  ma.m.gcap = cap;
-  ma.m.stride = cap + 8;
-  ma.m.nwords = mw;
-  ma.m.has_ident2 = kp.has_ident2() ? 1 : 0;
-  w = 1;
-  if (kp.has_ident2()) ma.m.ops[w++] = 255;
-  if (kp.need_first_row) ma.m.ops[w++] = 2;
-  for (const auto& sw : kp.states) ma.m.ops[w++] = uint32_t(sw.op);
-  for (const auto& ag : kp.aggs) {
-    if (ag.distinct_index >= 0) ma.m.ops[kp.state_word_base() + ag.first_word] = kMergeSkip;
-  }
-  ma.m.status = head->d_status;
-  ma.state_words = W;
-  ma.first_row_word = resolved ? uint32_t(kp.first_row_word()) : 0xffffffffu;
-  ma.ncols = nc;
-  uint64_t* d_ngroups = head->d_counters + 4;
-  ma.m.exclusive = 1;  // (one launch per table, a table's groups are pairwise different)
-  ma.m.fresh = d_ngroups;
-  HIP_TRY(hipMemsetAsync(d_ngroups, 0, 8, s));
-  HIP_TRY(hipMemsetAsync(head->d_status, 0, 16, s));
-
-  // ---- table by table: records -> wire form -> merge -----------------------------------------
-  DevBuf<uint64_t> d_rec, d_wire, d_sizes;
-  DevBuf<RtColumn> d_cols;
-  DevBuf<uint8_t> d_heap;
-  HIP_TRY(d_rec.alloc(std::max<uint64_t>(max_n, 1) * rw_in * 8));
-  if (resolved) {
-    HIP_TRY(d_wire.alloc(std::max<uint64_t>(max_n, 1) * rw * 8));
-    HIP_TRY(d_cols.alloc(std::max<uint32_t>(nc, 1) * sizeof(RtColumn)));
-  }
-  head->m_heap.clear();
-  uint64_t rows_scanned = 0, rows_passed = 0;
-  double kernel_ms = 0;
-  for (size_t pi = 0; pi < parts.size(); ++pi) {
-    evql_query* q = parts[pi];
-    evql_table* t = q->table;
-    rows_scanned += q->stats.rows_scanned;
-    rows_passed += q->stats.rows_passed;
-    kernel_ms += q->stats.kernel_ms;
-    const uint64_t n = q->ngroups;
-    if (n == 0) continue;
-    RecordsView view;
-    Status stv = query_records_view(q, &view);
-    if (!stv.ok()) return stv;
-    const uint64_t nd = view.nd;
-    if (nd) HIP_TRY(hipMemcpyAsync(d_rec, view.dense, nd * rw_in * 8, hipMemcpyDeviceToDevice, s));
-    if (n > nd) {
-      uint64_t* d_cnt = q->d_counters + 6;
-      HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-      HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, W, d_rec.p + nd * rw_in, n - nd,
-                                   d_cnt, s));
-    }
-    if (!resolved) {
-      HIP_TRY(launch_table_merge(ma.m, d_rec, n, s));
-      continue;
-    }
-    std::vector<RtColumn> rc(nc);
-    std::vector<uint32_t> str_cols;
-    uint64_t str_mask = 0;
-    for (uint32_t c = 0; c < nc; ++c) {
-      const ColAccess& ca = q->rplan().cols[c];
-      rc[c] = RtColumn{};
-      rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
-      rc[c].mode = ca.mode;
-      rc[c].bits = ca.bits;
-      if (q->nested) {
-        // first rows of a nested scan are FLATTENED rows: the operator's own columns
-        // (fetch_results gathers from the same sources)
-        if (ca.packed) {
-          rc[c].pages = nullptr;
-          rc[c].base = q->nested_packed[c].base;
-        }
-        rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
-      } else if (ca.packed) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
-        rc[c].base = m.d_packed;
-      } else if (ca.mode == ColAccess::SOA) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
-        rc[c].tags = m.d_tags;
-      }
-      if (ca.string_hash) {
-        str_mask |= 1ull << c;
-        str_cols.push_back(c);
-      }
-    }
-    if (str_cols.size() > kMaxWireStrCols) {
-      return Status::error(EVQL_ENOTSUP, "too many string columns in a chain plan");
-    }
-    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-    ResolveArgs ra{};
-    ra.image = t->d_image;
-    ra.cols = d_cols;
-    ra.ncols = nc;
-    ra.in_words = rw_in;
-    ra.first_row_word = uint32_t(1 + kp.first_row_word());
-    ra.rank_tag = uint64_t(pi) << 44;
-    ra.in = d_rec;
-    ra.n = n;
-    ra.out = d_wire;
-    HIP_TRY(launch_resolve_records(ra, s));
-    uint64_t heap_bytes = 0;
-    if (!str_cols.empty()) {
-      WireStrArgs wa{};
-      wa.image = t->d_image;
-      wa.records = d_wire;
-      wa.n = n;
-      wa.rw = rw;
-      wa.tags_word = rw_in + nc;
-      wa.nstr = uint32_t(str_cols.size());
-      for (size_t k = 0; k < str_cols.size(); ++k) {
-        wa.word[k] = rw_in + str_cols[k];
-        wa.col[k] = str_cols[k];
-        wa.pages[k] = t->d_pages[q->rplan().cols[str_cols[k]].layout_index][0];
-      }
-      HIP_TRY(d_sizes.alloc((n + 4) * 8));
-      wa.sizes = d_sizes;
-      wa.nranks = 1;
-      const uint64_t seg[2] = {0, n};
-      uint64_t* d_seg = d_sizes.p + n + 2;
-      HIP_TRY(hipMemcpyAsync(d_seg, seg, 16, hipMemcpyHostToDevice, s));
-      wa.starts = d_seg;
-      HIP_TRY(launch_wire_str_sizes(wa, s));
-      HIP_TRY(launch_exclusive_scan(d_sizes, n, d_sizes.p + n, s));
-      HIP_TRY(hipMemcpyAsync(&heap_bytes, d_sizes.p + n, 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      HIP_TRY(d_heap.alloc(heap_bytes + 16));
-      wa.heap = d_heap;
-      HIP_TRY(launch_wire_str_copy(wa, s));
-    }
-    ma.str_mask = str_mask;
-    ma.heap_base = head->m_heap.size();
-    HIP_TRY(launch_table_merge_resolved(ma, d_wire, n, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (rc / seg live until here)
-    if (heap_bytes) {
-      const size_t old = head->m_heap.size();
-      // the same bytes stay on the device: an exchange of this head exports them from there
-      if (old + heap_bytes > head->mheap_cap) {
-        const uint64_t want = std::max<uint64_t>(2 * head->mheap_cap, old + heap_bytes + 4096);
-        DevBuf<uint8_t> grown;
-        HIP_TRY(grown.alloc(want));
-        if (old) HIP_TRY(hipMemcpyAsync(grown, head->d_mheap, old, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        head->d_mheap = std::move(grown);
-        head->mheap_cap = want;
-      }
-      HIP_TRY(hipMemcpyAsync(head->d_mheap.p + old, d_heap, heap_bytes, hipMemcpyDeviceToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));  // (d_heap is allocated anew for the next table)
-      head->m_heap.resize(old + heap_bytes);
-      HIP_TRY(hipMemcpy(head->m_heap.data() + old, d_heap, heap_bytes, hipMemcpyDeviceToHost));
-    }
-  }
-  if (head->m_heap.size() > kStrOffMask) {
-    return Status::error(EVQL_ENOTSUP, "chain: first-row strings exceed the offset range");
-  }
-  // ---- count_distinct: the union of the tables' pair sets ---------------------------------------
-  if (kp.n_distinct > 0) {
-    std::vector<uint64_t> counts(size_t(kp.n_distinct) * parts.size(), 0);
-    uint64_t max_total = 0;
-    for (int d = 0; d < kp.n_distinct; ++d) {
-      uint64_t tot = 0;
-      for (size_t pi = 0; pi < parts.size(); ++pi) {
-        evql_query* q = parts[pi];
-        if (!q->d_pairset[d]) continue;
-        uint64_t* d_cnt = q->d_counters + 6;
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-        HIP_TRY(launch_pairset_export(q->d_pairset[d], q->pairset_cap, nullptr, 0, d_cnt, s));
-        HIP_TRY(hipMemcpyAsync(&counts[size_t(d) * parts.size() + pi], d_cnt, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        tot += counts[size_t(d) * parts.size() + pi];
-      }
-      max_total = std::max(max_total, tot);
-    }
-    uint64_t set_cap = 1 << 16;
-    while (set_cap < max_total * 2) set_cap <<= 1;
-    for (const auto& ag : kp.aggs) {
-      if (ag.distinct_index < 0) continue;
-      const int d = ag.distinct_index;
-      uint64_t tot = 0;
-      for (size_t pi = 0; pi < parts.size(); ++pi) tot += counts[size_t(d) * parts.size() + pi];
-      DevBuf<uint64_t> d_tr;
-      HIP_TRY(d_tr.alloc(std::max<uint64_t>(tot, 1) * 24));
-      uint64_t off = 0;
-      for (size_t pi = 0; pi < parts.size(); ++pi) {
-        evql_query* q = parts[pi];
-        const uint64_t np = counts[size_t(d) * parts.size() + pi];
-        if (!np) continue;
-        uint64_t* d_cnt = q->d_counters + 6;
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-        HIP_TRY(launch_pairset_export(q->d_pairset[d], q->pairset_cap, d_tr.p + off * 3, np, d_cnt, s));
-        off += np;
-      }
-      if (head->d_mset[d] && head->mset_cap[d] != set_cap) {
-        hipFree(head->d_mset[d]);
-        head->d_mset[d] = nullptr;
-      }
-      if (!head->d_mset[d]) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&head->d_mset[d]), set_cap * 24));
-      }
-      head->mset_cap[d] = set_cap;
-      uint64_t* d_set = head->d_mset[d];
-      HIP_TRY(hipMemsetAsync(d_set, 0xff, set_cap * 24, s));
-      PairsetMergeArgs pa{};
-      pa.set = d_set;
-      pa.set_cap = set_cap;
-      pa.words = head->d_mtab;
-      pa.gcap = cap;
-      pa.nwords = mw;
-      pa.word = uint32_t(kp.state_word_base() + ag.first_word);
-      pa.key_mode = uint32_t(kp.key_mode);
-      pa.status = head->d_status;
-      HIP_TRY(launch_pairset_merge(pa, d_tr, tot, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      // (PARTIAL emission reads the values of every group from the merged set,
-      // fetch_results)
-    }
-  }
-  uint32_t status[4] = {0};
-  HIP_TRY(hipMemcpyAsync(status, head->d_status, 16, hipMemcpyDeviceToHost, s));
-  uint64_t ng = 0;
-  HIP_TRY(hipMemcpyAsync(&ng, d_ngroups, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (status[0] & 2u) return Status::error(EVQL_ENOMEM, "merged group table full");
-  if (status[0] & 8u) return Status::error(EVQL_ENOMEM, "merged count_distinct set full");
-  head->merged = true;
-  head->chain_merged = true;
-  head->ngroups = ng;
-  head->stats.num_groups = ng;
-  head->stats.rows_scanned = rows_scanned;
-  head->stats.rows_passed = rows_passed;
-  head->stats.kernel_ms = kernel_ms;
-  head->stats.total_ms = kernel_ms;
-  head->fetched = false;
-  head->emit_pos = 0;
-  return Status();
-}
-
-}  // namespace evql
 
 // ---------------------------------------------------------------------------------------
 // C ABI

@@ -43,18 +43,6 @@ namespace evql {
 // ---------------------------------------------------------------------------
 // query execution
 // ---------------------------------------------------------------------------
-static uint64_t word_identity(int op) {
-  switch (op) {
-    case 2: return 0xFFFFFFFFFFFFFFFFull;
-    case 3: return 0ull;
-    case 4: return 0x7FFFFFFFFFFFFFFFull;
-    case 5: return 0x8000000000000000ull;
-    case 6: return 0x7FF0000000000000ull;
-    case 7: return 0xFFF0000000000000ull;
-    default: return 0ull;
-  }
-}
-
 // an empty group table: every word of every slot at its operation's identity
 static hipError_t init_gtab(const evql_query* q, hipStream_t s) {
   const KernelPlan& kp = q->kp;
@@ -62,11 +50,7 @@ static hipError_t init_gtab(const evql_query* q, hipStream_t s) {
   ia.words = q->d_gtab;
   ia.stride = q->gcap + 8;
   ia.nwords = uint32_t(kp.words_per_slot());
-  ia.identity[0] = 0xFFFFFFFFFFFFFFFFull;
-  int w = 1;
-  if (kp.has_ident2()) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  if (kp.need_first_row) ia.identity[w++] = 0xFFFFFFFFFFFFFFFFull;
-  for (const auto& sw : kp.states) ia.identity[w++] = word_identity(sw.op);
+  slot_identities(kp, ia.nwords, ia.identity);
   return launch_table_init(ia, s);
 }
 
@@ -476,7 +460,7 @@ Status query_launch(evql_query* q) {
     HIP_TRY(hipMemsetAsync(q->d_status, 0, 16, s));
     HIP_TRY(hipMemsetAsync(q->d_counters, 0, 64, s));
   } else {
-    HIP_TRY(hipMemsetAsync(q->d_counters + 4, 0, 8, s));  // (the group count is recounted)
+    HIP_TRY(hipMemsetAsync(q->d_counters + kFreshGroupCounter, 0, 8, s));  // (the group count is recounted)
   }
 
   HostArgs a{};
@@ -596,7 +580,7 @@ Status query_launch(evql_query* q) {
     HIP_TRY(hipEventRecord(q->ev1, s));
     // group count into counter word 4 (read back by finish together with the rest)
     HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, uint32_t(kp.words_per_slot()),
-                                 nullptr, 0, q->d_counters + 4, s));
+                                 nullptr, 0, q->d_counters + kFreshGroupCounter, s));
     q->launched = true;
     q->stats.n_kernel_launches = 7;
     q->stats.rows_scanned = a.row_end - a.row_begin;
@@ -614,7 +598,7 @@ Status query_launch(evql_query* q) {
   HIP_TRY(hipEventRecord(q->ev1, s));
   // group count into counter word 4 (read back by finish together with the rest)
   HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, uint32_t(kp.words_per_slot()),
-                               nullptr, 0, q->d_counters + 4, s));
+                               nullptr, 0, q->d_counters + kFreshGroupCounter, s));
   q->launched = true;
   q->stats.n_kernel_launches = 3;
   q->stats.rows_scanned = a.row_end - a.row_begin;
@@ -640,7 +624,7 @@ Status query_records_view(evql_query* q, RecordsView* v) {
     if (n > nd) {  // groups of overflowed buckets / of the LDS path sit in the HBM table
       HIP_TRY(tmp.alloc(n * in_words * 8));
       if (nd) HIP_TRY(hipMemcpyAsync(tmp, q->d_dense, nd * in_words * 8, hipMemcpyDeviceToDevice, s));
-      uint64_t* d_cnt = q->d_counters + 6;
+      uint64_t* d_cnt = q->d_counters + kScratchCounter;
       HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
       HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, in_words - 1,
                                    tmp.p + nd * in_words, n - nd, d_cnt, s));
@@ -757,7 +741,7 @@ Status query_finish(evql_query* q) {
 // (import of another partition's groups)
 Status query_recount(evql_query* q) {
   evql_ctx* ctx = q->ctx;
-  uint64_t* d_cnt = q->d_counters + 4;
+  uint64_t* d_cnt = q->d_counters + kFreshGroupCounter;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
   HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, uint32_t(q->kp.words_per_slot()),
                                nullptr, 0, d_cnt, ctx->stream));
@@ -785,7 +769,7 @@ static Status rebuild_table(evql_query* q, uint64_t total) {
   DevBuf<uint64_t> old_rec;
   if (in_table) {
     HIP_TRY(old_rec.alloc(in_table * (nwords + 1) * 8));
-    uint64_t* d_cnt = q->d_counters + 6;
+    uint64_t* d_cnt = q->d_counters + kScratchCounter;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
     HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, nwords, old_rec, in_table, d_cnt, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -799,12 +783,7 @@ static Status rebuild_table(evql_query* q, uint64_t total) {
   a.words = q->d_gtab;
   a.gcap = q->gcap;
   a.stride = q->gcap + 8;
-  a.nwords = nwords;
-  int w = 1;
-  a.has_ident2 = kp.has_ident2() ? 1 : 0;
-  if (kp.has_ident2()) a.ops[w++] = 255;
-  if (kp.need_first_row) a.ops[w++] = 2;  // min
-  for (const auto& sw : kp.states) a.ops[w++] = uint32_t(sw.op);
+  merge_ops(kp, false, &a);
   a.status = q->d_status;
   HIP_TRY(hipMemsetAsync(q->d_status, 0, 16, s));
   if (in_table) HIP_TRY(launch_table_merge(a, old_rec, in_table, s));
@@ -812,7 +791,7 @@ static Status rebuild_table(evql_query* q, uint64_t total) {
   uint32_t status[4] = {0};
   HIP_TRY(hipMemcpyAsync(status, q->d_status, 16, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (status[0] & 2u) return Status::error(EVQL_ENOMEM, "group table full");
+  if (status[0] & 2u) return merge_status_error(2u, "");
   q->dense_n = 0;
   return Status();
 }
@@ -846,11 +825,8 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
   std::vector<uint64_t> held(kp.n_distinct, 0);
   for (int d = 0; d < kp.n_distinct; ++d) {
     if (!q->d_pairset[d]) continue;
-    uint64_t* d_cnt = q->d_counters + 6;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
-    HIP_TRY(launch_pairset_export(q->d_pairset[d], q->pairset_cap, nullptr, 0, d_cnt, s));
-    HIP_TRY(hipMemcpyAsync(&held[d], d_cnt, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    Status stc = pairset_count(q, q->d_pairset[d], q->pairset_cap, &held[d]);
+    if (!stc.ok()) return stc;
     held_max = std::max(held_max, held[d]);
   }
   const uint64_t need = std::max(held_max, held[which] + n);
@@ -864,7 +840,7 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
       HIP_TRY(hipMemsetAsync(d_new, 0xff, cap * 24, s));
       if (q->d_pairset[d] && held[d]) {
         HIP_TRY(d_tr.alloc(held[d] * 24));
-        uint64_t* d_cnt = q->d_counters + 6;
+        uint64_t* d_cnt = q->d_counters + kScratchCounter;
         HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
         HIP_TRY(launch_pairset_export(q->d_pairset[d], q->pairset_cap, d_tr, held[d], d_cnt, s));
         PairsetMergeArgs pa{};
@@ -904,8 +880,8 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
   uint32_t status[4] = {0};
   HIP_TRY(hipMemcpyAsync(status, q->d_status, 16, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (status[0] & 8u) return Status::error(EVQL_ENOMEM, "count_distinct set full");
-  if (status[0] & 2u) {
+  if (status[0] & 8u) return merge_status_error(8u, "");
+  if (status[0] & 2u) {  // (here: the kernel found no slot with the pair's identity)
     return Status::error(EVQL_EARG, "a pair's group is not in the table: import the group records first");
   }
   q->fetched = false;

@@ -109,23 +109,9 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
   const uint32_t nc = uint32_t(kp.cols.size());
   if (need_first) {
     // the column values of every group's first row (strings: their strpos words)
-    std::vector<RtColumn> rc(nc);
-    for (uint32_t c = 0; c < nc; ++c) {
-      const ColAccess& ca = kp.cols[c];
-      rc[c] = RtColumn{};
-      rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
-      rc[c].mode = ca.mode;
-      rc[c].bits = ca.bits;
-      if (ca.packed) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].pages = nullptr;  // (a flat array: ColAccess::NARROW)
-        rc[c].base = m.d_packed;
-      } else if (ca.mode == ColAccess::SOA) {
-        const MaterializedColumn& m = t->materialized[ca.name];
-        rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
-        rc[c].tags = m.d_tags;
-      }
-    }
+    std::vector<RtColumn> rc;
+    Status stc = first_row_columns(q, &rc);
+    if (!stc.ok()) return stc;
     HIP_TRY(d_rows.alloc(n * 8));
     HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
     HIP_TRY(d_vals.alloc(n * nc * 8));
@@ -385,29 +371,9 @@ static Status first_rows_from_table(evql_query* q, uint64_t n, uint32_t nwords) 
       return Status::error(EVQL_ERUNTIME, "a group's first row was not recorded");
     }
   }
-  std::vector<RtColumn> rc(nc);
-  for (uint32_t c = 0; c < nc; ++c) {
-    const ColAccess& ca = kp.cols[c];
-    rc[c].pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
-    rc[c].mode = ca.mode;
-    rc[c].bits = ca.bits;
-    if (ca.packed && q->nested) {
-      rc[c].pages = nullptr;
-      rc[c].base = q->nested_packed[c].base;
-    } else if (ca.packed) {
-      const MaterializedColumn& m = t->materialized[ca.name];
-      rc[c].pages = nullptr;
-      rc[c].base = m.d_packed;
-    }
-    if (q->nested) {
-      rc[c].soa = ca.string_hash ? q->nested_strpos[c] : q->nested_flat[c];
-    } else if (ca.mode == ColAccess::SOA) {
-      const MaterializedColumn& m = t->materialized[ca.name];
-      // strings: (len << 40 | position); their bytes are copied out below
-      rc[c].soa = ca.string_hash ? m.d_strpos : m.d_values;
-      rc[c].tags = m.d_tags;
-    }
-  }
+  std::vector<RtColumn> rc;
+  Status stc = first_row_columns(q, &rc);
+  if (!stc.ok()) return stc;
   DevBuf<uint64_t> d_rows, d_vals;
   DevBuf<RtColumn> d_cols;
   DevBuf<uint8_t> d_tags;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -289,7 +290,7 @@ struct evql_query {
   uint64_t reported_rows_scanned = ~0ull;  // != ~0: the reference's count, where it is not the row range
   // evql_query_create_chain: this query scans the first table of a partition's chain;
   // `chain` holds the queries of the tables behind it (owned).  After execute their
-  // groups are merged in chain order into d_mtab (exchange.cc chain_merge).
+  // groups are merged in chain order into d_mtab (chain_merge.cc).
   std::vector<evql_query*> chain;
   // partitioned path buffers
   uint32_t* d_part_counts = nullptr;
@@ -573,7 +574,7 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
                        uint64_t offset);
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
 
-// exchange.cc / lsm.cc
+// chain_merge.cc / lsm.cc
 Status chain_merge(evql_query* head);
 size_t lsm_chain_parts(const evql_lsm_chain* ch, std::vector<evql_table*>* tables,
                        std::vector<const uint8_t*>* d_filters);
@@ -585,6 +586,58 @@ struct RecordsView {
   uint64_t nd = 0;
 };
 Status query_records_view(evql_query* q, RecordsView* out);
+
+// group_records.cc: groups that leave the scan (group imports, chain_merge.cc, exchange.cc)
+static const int kFreshGroupCounter = 4;  // d_counters word: occupied slots (a launch / a merge)
+static const int kScratchCounter = 6;     // d_counters word: records / triples a kernel wrote
+static const uint32_t kMergeSkip = 254;   // (rt_atomic knows no such op: the word is left alone)
+// A group outside the scan: a dense record [kind, slot words of rplan()] of rw_in words; sent
+// by plans that read first-row values as a wire record of rw words (+ one value word per scan
+// column, strings as len << 40 | heap offset, + one word of NULL tags); merged into a slot of
+// mw words (a wire record without its kind).
+struct GroupRecordLayout {
+  uint32_t W = 0, nc = 0;  // slot words of the scan's table, scan columns
+  bool resolved = false;   // first-row values travel in the records (need_first_row)
+  uint32_t rw_in = 0, rw = 0, mw = 0;
+  std::vector<uint32_t> str_cols;  // the string columns among the resolved ones
+  uint64_t str_mask = 0;
+  uint32_t first_row_word = 0xffffffffu;  // slot word of the first row (all ones: none)
+  uint32_t has_ident2 = 0;
+};
+GroupRecordLayout group_record_layout(const KernelPlan& kp);
+// what a merged table / the string kernels cannot hold (plan_kind: "an exchanged", "a chain")
+Status group_record_layout_check(const GroupRecordLayout& L, const char* plan_kind);
+// an empty slot's first nwords words: all ones (identity, first row), the states' identities, 0
+void slot_identities(const KernelPlan& kp, uint32_t nwords, uint64_t* out);
+// a->nwords (words_per_slot), has_ident2, ops[]; skip_distinct: count_distinct words stay as
+// they are (kMergeSkip): they count the pairs of the MERGED set, which are inserted separately
+void merge_ops(const KernelPlan& kp, bool skip_distinct, MergeArgs* a);
+// row-addressable views of q's scan columns, for gathers at the groups' first rows
+Status first_row_columns(evql_query* q, std::vector<RtColumn>* out);
+// n dense records -> wire records; *rc (host copy of d_cols) lives until the next synchronisation
+Status resolve_first_rows(evql_query* q, const GroupRecordLayout& L, uint64_t rank_tag,
+                          std::vector<RtColumn>* rc, RtColumn* d_cols, const uint64_t* in, uint64_t n,
+                          uint64_t* out);
+// q's ngroups groups (view: query_records_view) as one run of dense records at dst
+Status query_dense_records(evql_query* q, const GroupRecordLayout& L, const RecordsView& view,
+                           uint64_t* dst);
+// stored triples of a pair set (NULL: none) -> *n; one synchronisation
+Status pairset_count(evql_query* q, const uint64_t* set, uint64_t cap, uint64_t* n);
+// q->d_mtab as an empty table for total_records groups at load factor <= 1/2 (a failed
+// allocation leaves d_mtab NULL and mcap 0); *ma ready for one merge launch per rank / table
+Status merged_table_prepare(evql_query* q, const GroupRecordLayout& L, uint64_t total_records,
+                            MergeResolvedArgs* ma);
+// q->d_mset[which] as an empty set of cap slots, then n triples inserted (counted in `word`)
+Status merged_set_fill(evql_query* q, const GroupRecordLayout& L, int which, uint64_t cap,
+                       uint32_t word, const uint64_t* d_triples, uint64_t n);
+// The string words of n wire records (nseg owner segments, seg[nseg + 1] their first records)
+// become offsets into a heap of heap_for(bytes) (NULL = failed), which gets the bytes (from
+// `flat`, or the columns' pages); segoff[nseg + 1]: byte offset of every segment.  One sync.
+Status wire_strings(evql_query* q, const GroupRecordLayout& L, const uint8_t* flat, uint64_t* records,
+                    uint64_t n, const uint64_t* seg, uint32_t nseg, uint64_t* d_sizes, uint64_t* d_seg,
+                    const std::function<uint8_t*(uint64_t)>& heap_for, uint64_t* segoff);
+// d_status word 0 behind a merge: bit 1 = the group table is full, bit 3 = a pair set is
+Status merge_status_error(uint32_t status, const char* what);
 // device_writer.cc: a cstable v0.2.0 image encoded on the device from SoA columns
 struct DeviceColumnIn {
   const uint64_t* values;  // device, num_rows value words

@@ -74,7 +74,7 @@ static Status build_dict(evql_table* t, int li, StringDict* d) {
     const uint64_t nd = std::min(dq->dense_n, D);
     if (nd) HIP_TRY(hipMemcpyAsync(d_rec, dq->d_dense, nd * (W + 1) * 8, hipMemcpyDeviceToDevice, s));
     if (D > nd) {
-      uint64_t* d_cnt = dq->d_counters + 6;
+      uint64_t* d_cnt = dq->d_counters + kScratchCounter;
       HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
       HIP_TRY(launch_table_compact(dq->d_gtab, dq->gcap, dq->gcap + 8, W, d_rec.p + nd * (W + 1),
                                    D - nd, d_cnt, s));

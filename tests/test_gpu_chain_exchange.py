@@ -430,6 +430,38 @@ def test_nested_chain_heads_exchange(name):
     check_modes(res, exp, 1)
 
 
+class MappedKey:
+    """an expected result whose key column went through `fn` (NULL stays NULL)"""
+    def __init__(self, exp, fn):
+        self.types, self.nrows = exp.types, exp.nrows
+        self._rows = [((None if r[0] is None else fn(r[0])),) + tuple(r[1:]) for r in exp.rows()]
+
+    def rows(self):
+        return self._rows
+
+
+@pytest.mark.parametrize("name", ["leaf-key", "string-key", "leaf-expr"])
+def test_nested_operators_without_a_chain_exchange(name):
+    """Nested operators that are no chain heads (one file each, no filter): their first-row
+    values -- flattened rows, one column of them with a narrow copy -- are resolved by the
+    exchange itself.  `leaf-expr` evaluates its select expression on the group's first row;
+    the value depends on the key alone, so which row is first does not matter: the expected
+    rows are the oracle's for the bare key with the key mapped k -> 2k + 1."""
+    lpos, lprice = col("items.position"), col("items.price")
+    kw = {"leaf-key": dict(select=[lpos, count(1), sum_(lprice)], group_by=[lpos]),
+          "string-key": dict(select=[col("s"), count(1), sum_(lpos)], group_by=[col("s")]),
+          "leaf-expr": dict(select=[lpos * 2 + 1, count(1)], group_by=[lpos])}[name]
+    kw = dict(kw, scan_mode=K.SCAN_NESTED)
+    specs = [("plain", LN, "single_plain"), ("plain", LN, "single")]
+    if name == "leaf-expr":
+        exp = MappedKey(nested_expected(specs, dict(kw, select=[lpos, count(1)])),
+                        lambda k: 2 * k + 1)
+    else:
+        exp = nested_expected(specs, kw)
+    res = run_ranks(specs, exchange_body(LN.NESTED_LSM_SCHEMA, kw, [GATHER, OWNER]))
+    check_modes(res, exp, 1)
+
+
 # ---------------------------------------------------------------------------------------
 # 7. a chain of one file (no chain_merge) beside a chain of several
 # ---------------------------------------------------------------------------------------

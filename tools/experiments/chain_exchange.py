@@ -22,8 +22,9 @@ those chain_merge may launch over the files' own tables by their position in the
 Recorded per G: both kernels'
 times (minimum and range), the bytes either reads -- (mcap + 8) * m_words * 8, mcap = the
 capacity chain_merge gives the merged table: the power of two >= 65536 that holds twice the
-sum of the files' group counts --, the bytes per second at the minimum, and export_ms of
-evql_exchange_last_stats (host clock from the call's entry to the end of its export steps).
+sum of the files' group counts --, the bytes per second at the minimum, and export_ms, transfer_ms
+and merge_ms of evql_exchange_last_stats (host clock: from the call's entry to the end of its
+export steps, then the collectives and copies, then the merge up to the call's return).
 One device only: transfer and merge are exercised, not measured as a multi-GPU figure.
 
 usage: chain_exchange.py [--groups G[,G..]] [--reps R] [--out FILE]"""
@@ -68,13 +69,15 @@ def child(groups, reps):
     q.set_order(Order(plan, [(1, True)], limit=1))
     m_words = q.record_words() - 1
     out = dict(groups_asked=groups, rows_per_file=2 * groups, groups_per_file=per_file,
-               m_words=m_words, export_ms=[], merged_groups=None, exchanged_groups=None)
+               m_words=m_words, export_ms=[], transfer_ms=[], merge_ms=[], merged_groups=None,
+               exchanged_groups=None)
     for _ in range(reps):
         q.execute()
         out["merged_groups"] = q.stats()["num_groups"]
         q.exchange(x, K.EXCHANGE_GATHER_ALL)
         st = x.stats()
-        out["export_ms"].append(st["export_ms"])
+        for phase in ("export_ms", "transfer_ms", "merge_ms"):
+            out[phase].append(st[phase])
         out["exchanged_groups"] = st["groups_received"]
         out["merge_buckets"] = st["merge_buckets"]
         q.execute()
@@ -145,7 +148,8 @@ def measure(groups, reps):
         yard = [tables[r * (2 * c + 1) + c] for r in range(reps)]
         res["k_mtab_compact_ms"] = spread(new)
         res["k_table_compact_ms"] = spread(yard)
-        res["export_ms"] = spread(res["export_ms"])
+        for phase in ("export_ms", "transfer_ms", "merge_ms"):
+            res[phase] = spread(res[phase])
         b = res["bytes_read"]
         res["k_mtab_compact_GBps"] = b / (min(new) * 1e6)
         res["k_table_compact_GBps"] = b / (min(yard) * 1e6)
