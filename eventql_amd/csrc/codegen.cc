@@ -13,6 +13,14 @@ const char* device_library_source() {
 
 namespace {
 
+// string functions per row: part of the generated text of the plans that use one
+const char* strfn_library_source() {
+  static const char* src =
+#include "evql_strfn.inc"
+      ;
+  return src;
+}
+
 const char* ctype(uint32_t t) {
   switch (t) {
     case EVQL_T_INT64: return "i64";
@@ -140,6 +148,47 @@ struct Emitter {
     return b;
   }
 
+  // set once the text uses a helper of evql_strfn.h (Gen::row_function puts it in front)
+  bool uses_strfn = false;
+
+  // A string value (planner.cc string_value_refusal) as a lazy value object of evql_strfn.h:
+  // the factory calls nest the way the tree nests, every function node becomes a `const
+  // auto` local, a column or literal the leaf over str_operand.  Returns the expression
+  // that names the value.
+  std::string str_value(const ExprPtr& x) {
+    uses_strfn = true;
+    if (x->kind != Expr::CALL) return "evql_sx_leaf(" + str_operand(x) + ")";
+    std::string rhs;
+    switch (x->family) {
+      case EVQL_FAM_LCASE: rhs = "evql_sx_lcase(" + str_value(x->args[0]) + ")"; break;
+      case EVQL_FAM_UCASE: rhs = "evql_sx_ucase(" + str_value(x->args[0]) + ")"; break;
+      case EVQL_FAM_LTRIM: rhs = "evql_sx_ltrim(" + str_value(x->args[0]) + ")"; break;
+      case EVQL_FAM_RTRIM: rhs = "evql_sx_rtrim(" + str_value(x->args[0]) + ")"; break;
+      case EVQL_FAM_CONCAT: {
+        const std::string a = str_value(x->args[0]), b = str_value(x->args[1]);
+        rhs = "evql_sx_concat(" + a + ", " + b + ")";
+        break;
+      }
+      case EVQL_FAM_SUBSTRING: {
+        // (a literal position is a pooled kernel argument like any numeric literal)
+        const std::string a = str_value(x->args[0]);
+        const Val p = emit(x->args[1]);
+        rhs = "evql_sx_substring(" + a + ", (i64) " + p.v + ")";
+        break;
+      }
+      default: {  // EVQL_FAM_TO_STRING
+        const Val v = emit(x->args[0]);
+        const std::string null = "((" + v.g + " & 1u) != 0)";
+        if (x->type_slot == EVQL_TS_BOOL) rhs = "evql_sx_bool(" + v.v + ", " + null + ")";
+        else if (x->type_slot == EVQL_TS_INT64) rhs = "evql_sx_i64((i64) " + v.v + ", " + null + ")";
+        else rhs = "evql_sx_u64((u64) " + v.v + ", " + null + ")";
+      }
+    }
+    const std::string t = fresh("s");
+    o << ind << "const auto " << t << " = " << rhs << ";\n";
+    return t;
+  }
+
   // payload reinterpreted as raw 64 bits
   static std::string as_bits(const Val& x) {
     switch (x.type) {
@@ -204,23 +253,41 @@ struct Emitter {
     const int fam = e->family, ts = e->type_slot;
     if (ts == EVQL_TS_STRING && ((fam >= EVQL_FAM_CMP && fam <= EVQL_FAM_GTE) ||
                                  fam == EVQL_FAM_STARTSWITH || fam == EVQL_FAM_ENDSWITH)) {
-      // operands are string columns / literals (planner.cc strings_lowerable)
-      const std::string l = str_operand(e->args[0]), r = str_operand(e->args[1]);
-      const std::string c = "evql_str_cmp(" + l + ", " + r + ")";
+      // operands are string values (planner.cc strings_refusal): two columns / literals go
+      // through evql_device.h's compares, a computed operand takes both through evql_strfn.h
+      const bool lazy = e->args[0]->kind == Expr::CALL || e->args[1]->kind == Expr::CALL;
+      const std::string fn = lazy ? "evql_sx_" : "evql_str_";
+      std::string l, r;
+      if (lazy) {
+        l = str_value(e->args[0]);
+        r = str_value(e->args[1]);
+      } else {
+        l = str_operand(e->args[0]);
+        r = str_operand(e->args[1]);
+      }
+      const std::string c = fn + "cmp(" + l + ", " + r + ")";
       std::string rhs;
       switch (fam) {
-        case EVQL_FAM_EQ: rhs = "evql_str_eq(" + l + ", " + r + ")"; break;
-        case EVQL_FAM_NEQ: rhs = "(!evql_str_eq(" + l + ", " + r + "))"; break;
+        case EVQL_FAM_EQ: rhs = fn + "eq(" + l + ", " + r + ")"; break;
+        case EVQL_FAM_NEQ: rhs = "(!" + fn + "eq(" + l + ", " + r + "))"; break;
         case EVQL_FAM_LT: rhs = "(" + c + " < 0)"; break;
         case EVQL_FAM_LTE: rhs = "(" + c + " <= 0)"; break;
         case EVQL_FAM_GT: rhs = "(" + c + " > 0)"; break;
         case EVQL_FAM_GTE: rhs = "(" + c + " >= 0)"; break;
-        case EVQL_FAM_STARTSWITH: rhs = "evql_str_affix(" + l + ", " + r + ", false)"; break;
-        case EVQL_FAM_ENDSWITH: rhs = "evql_str_affix(" + l + ", " + r + ", true)"; break;
+        case EVQL_FAM_STARTSWITH: rhs = fn + "affix(" + l + ", " + r + ", false)"; break;
+        case EVQL_FAM_ENDSWITH: rhs = fn + "affix(" + l + ", " + r + ", true)"; break;
         default: rhs = "((i64) " + c + ")";
       }
       std::string t = fresh("t");
       o << ind << "const " << ctype(e->type) << " " << t << " = " << rhs << ";\n";
+      return {t, "0u", e->type};
+    }
+    if (e->type == EVQL_T_STRING) {
+      // a computed string as a VALUE (a group key): the hash of its bytes, tag 0 like the
+      // result of every pure function
+      const std::string sv = str_value(e);
+      std::string t = fresh("t");
+      o << ind << "const u64 " << t << " = evql_sx_hash(" << sv << ");\n";
       return {t, "0u", e->type};
     }
     {

@@ -175,6 +175,10 @@ struct Gen {
     const std::string fn = s.str();
     s.str("");
     s << before;
+    if (em.uses_strfn && !strfn_emitted) {
+      s << strfn_library_source();
+      strfn_emitted = true;
+    }
     for (size_t i = 0; i < em.string_literals.size(); ++i) {
       const std::string& l = em.string_literals[i];
       s << "__device__ const u8 evql_slit" << (lit_base + i) << "[" << (l.empty() ? 1 : l.size())
@@ -187,6 +191,7 @@ struct Gen {
     return em.string_literals.size();
   }
 
+  bool strfn_emitted = false;  // evql_strfn.h is in the text
   size_t n_literals = 0;  // of evql_eval_row
   // numeric literals are numbered once per plan, across its row functions (A.lit[i])
   std::vector<uint64_t> pool;

@@ -55,25 +55,101 @@ bool is_string_compare(const ExprPtr& e) {
          e->family == EVQL_FAM_STARTSWITH || e->family == EVQL_FAM_ENDSWITH;
 }
 
-// Strings on the device: a bare column reference flows through untouched (as
-// its hash, for keys / first-row values), and string columns / literals may be
-// the operands of eq / neq / lt / lte / gt / gte / cmp / startswith / endswith (bytewise
-// compare in the kernel).  Anything else that produces or consumes a string (concat, IF over
-// strings, to_string ...) is not lowered.
-bool strings_lowerable(const ExprPtr& e, bool root = true) {
-  if (!e) return true;
-  if (e->type == EVQL_T_STRING) return root && e->kind == Expr::INPUT;
+// Strings on the device.  A string VALUE is a tree over string columns and literals of
+// lcase / ucase / ltrim / rtrim / substring / concat / to_string (of an integer, a timestamp
+// or a bool); the kernel evaluates it per row as a lazy (length, byte accessor) value
+// (codegen.cc str_value).  Such a value may be
+//   - the operand of eq / neq / lt / lte / gt / gte / cmp / startswith / endswith (bytewise);
+//   - a whole expression (`root`): a group key, which enters the identity as the 64-bit
+//     hash of its bytes -- a bare column as the hash the table keeps per row.
+// Anything else that produces or consumes a string (IF over strings, to_string of a
+// float64, a string as an aggregate's argument ...) is not lowered; nor is a string
+// function anywhere in a nested scan.
+//
+// The string-typed nodes of one value (columns and literals included) are limited: every
+// node is a struct of the generated text that the compiler has to keep in registers.
+const int kMaxStringNodes = 32;
+
+std::string strings_refusal(const ExprPtr& e, bool nested, bool root = true);
+
+// "" when the string value `e` can be evaluated per row; counts its string-typed nodes
+std::string string_value_refusal(const ExprPtr& e, bool nested, int* nodes) {
+  if (e->type != EVQL_T_STRING) return "string expression is not lowerable";
+  if (++*nodes > kMaxStringNodes) {
+    return "string expression of more than " + std::to_string(kMaxStringNodes) + " nodes is not lowered";
+  }
+  switch (e->kind) {
+    case Expr::INPUT:
+    case Expr::LITERAL:
+      return "";
+    case Expr::IF:
+      return "IF over strings is not lowered";
+    case Expr::CALL:
+      break;
+    default:
+      return "string expression is not lowerable";
+  }
+  if (nested) return "string functions in a nested scan are not lowered";
+  switch (e->family) {
+    case EVQL_FAM_LCASE:
+    case EVQL_FAM_UCASE:
+    case EVQL_FAM_LTRIM:
+    case EVQL_FAM_RTRIM:
+      return string_value_refusal(e->args[0], nested, nodes);
+    case EVQL_FAM_CONCAT: {
+      const std::string r = string_value_refusal(e->args[0], nested, nodes);
+      return r.empty() ? string_value_refusal(e->args[1], nested, nodes) : r;
+    }
+    case EVQL_FAM_SUBSTRING: {
+      const uint32_t pt = e->args[1]->type;
+      if (pt != EVQL_T_UINT64 && pt != EVQL_T_INT64 && pt != EVQL_T_TIMESTAMP64) {
+        return "substring position that is not an integer is not lowered";
+      }
+      const std::string r = string_value_refusal(e->args[0], nested, nodes);
+      return r.empty() ? strings_refusal(e->args[1], nested, false) : r;
+    }
+    case EVQL_FAM_TO_STRING:
+      switch (e->type_slot) {
+        case EVQL_TS_UINT64:
+        case EVQL_TS_INT64:
+        case EVQL_TS_TIMESTAMP64:
+        case EVQL_TS_BOOL:
+          if (e->args[0]->type == EVQL_T_STRING || e->args[0]->type == EVQL_T_FLOAT64 ||
+              e->args[0]->type == EVQL_T_NIL) {
+            return "string expression is not lowerable";
+          }
+          return strings_refusal(e->args[0], nested, false);
+        case EVQL_TS_FLOAT64:
+          return "to_string of a float64 is not lowered";
+        default:
+          return "string expression is not lowerable";
+      }
+    default:
+      return "string expression is not lowerable";
+  }
+}
+
+// "" when every string inside `e` is one the kernel can evaluate
+std::string strings_refusal(const ExprPtr& e, bool nested, bool root) {
+  if (!e) return "";
+  if (e->type == EVQL_T_STRING) {
+    if (!root) return "string expression is not lowerable";
+    int nodes = 0;
+    return string_value_refusal(e, nested, &nodes);
+  }
   if (is_string_compare(e)) {
     for (const auto& a : e->args) {
-      if (a->type != EVQL_T_STRING) return false;
-      if (a->kind != Expr::INPUT && a->kind != Expr::LITERAL) return false;
+      int nodes = 0;
+      const std::string r = string_value_refusal(a, nested, &nodes);
+      if (!r.empty()) return r;
     }
-    return true;
+    return "";
   }
   for (const auto& a : e->args) {
-    if (!strings_lowerable(a, false)) return false;
+    const std::string r = strings_refusal(a, nested, false);
+    if (!r.empty()) return r;
   }
-  return true;
+  return "";
 }
 
 // A predicate that holds for every row whatever the data: what the reference's planner
@@ -128,9 +204,12 @@ bool expr_always_true(const ExprPtr& e) {
 // marks the string columns whose bytes the kernel has to reach
 void mark_string_bytes(const ExprPtr& e, std::vector<ColAccess>* cols) {
   if (!e) return;
-  if (is_string_compare(e)) {
+  // (operands of a compare, and of the string functions of a computed value)
+  if (is_string_compare(e) || (e->kind == Expr::CALL && e->type == EVQL_T_STRING)) {
     for (const auto& a : e->args) {
-      if (a->kind == Expr::INPUT && a->input < cols->size()) (*cols)[a->input].string_bytes = true;
+      if (a->kind == Expr::INPUT && a->type == EVQL_T_STRING && a->input < cols->size()) {
+        (*cols)[a->input].string_bytes = true;
+      }
     }
   }
   for (const auto& a : e->args) mark_string_bytes(a, cols);
@@ -513,7 +592,9 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
     if (q->where.is_aggregate || q->where.return_type != EVQL_T_BOOL) {
       return Status::error(EVQL_EARG, "WHERE must be a non-aggregate boolean expression");
     }
-    if (!strings_lowerable(q->where.call)) return unsup("string expression is not lowerable");
+    // (a WHERE that is itself a string: rejected above, it is not boolean)
+    err = strings_refusal(q->where.call, nested, false);
+    if (!err.empty()) return unsup(err);
     q->has_where = true;
     kp.where = q->where.call;
     if (where_always_true) {
@@ -606,8 +687,16 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
     err = lower_program(plan->scan_select[i], &q->scan_select[i], &u);
     if (!err.empty()) return u ? unsup(err) : Status::error(EVQL_EARG, err);
     if (q->scan_select[i].is_aggregate) return unsup("aggregate in the scan select list");
-    if (!strings_lowerable(q->scan_select[i].call)) return unsup("string expression is not lowerable");
-    scan_out.push_back(q->scan_select[i].call);
+    // A bare scan's select list leaves the device as it is: a string only as the bytes of a
+    // bare column.  Above it, a scan select expression reaches the kernel inlined into the
+    // group and aggregate expressions, which are checked below.
+    const ExprPtr& se = q->scan_select[i].call;
+    if (bare && se && se->type == EVQL_T_STRING && se->kind != Expr::INPUT) {
+      return unsup("string-producing expressions in a bare scan's select list are not lowered");
+    }
+    err = strings_refusal(se, nested);
+    if (!err.empty()) return unsup(err);
+    scan_out.push_back(se);
   }
   if (bare) {
     // the scan select list is the output: every expression is evaluated by the kernel for
@@ -638,7 +727,8 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
     if (q->group[i].is_aggregate) return Status::error(EVQL_EARG, "aggregate in GROUP BY");
     ExprPtr g = inline_inputs(q->group[i].call, scan_out, &err);
     if (!err.empty()) return Status::error(EVQL_EARG, err);
-    if (!strings_lowerable(g)) return unsup("string expression is not lowerable");
+    err = strings_refusal(g, nested);
+    if (!err.empty()) return unsup(err);
     mark_string_bytes(g, &kp.cols);
     kp.group.push_back(g);
   }
@@ -669,7 +759,9 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
         if (lp.acc_args.size() != 1) return Status::error(EVQL_EARG, "aggregate arity");
         a.arg = inline_inputs(lp.acc_args[0], scan_out, &err);
         if (!err.empty()) return Status::error(EVQL_EARG, err);
-        if (!strings_lowerable(a.arg, false)) return unsup("string aggregates are not lowered");
+        if (a.arg && a.arg->type == EVQL_T_STRING) return unsup("string aggregates are not lowered");
+        err = strings_refusal(a.arg, nested, false);
+        if (!err.empty()) return unsup(err);
         mark_string_bytes(a.arg, &kp.cols);
       } else if (lp.acc_args.size() == 1 && lp.acc_args[0]->kind == Expr::CALL &&
                  lp.acc_args[0]->family == EVQL_FAM_TO_NIL) {
@@ -677,7 +769,9 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
         // it is not a plain column / literal
         const ExprPtr& inner = lp.acc_args[0]->args[0];
         if (inner->kind == Expr::CALL || inner->kind == Expr::IF) {
-          if (!strings_lowerable(inner, false)) return unsup("string expression is not lowerable");
+          if (inner->type == EVQL_T_STRING) return unsup("string aggregates are not lowered");
+          err = strings_refusal(inner, nested, false);
+          if (!err.empty()) return unsup(err);
         }
       }
       a.first_word = int(kp.states.size());
@@ -742,7 +836,7 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
       if (has_agg_get(lp.call)) return Status::error(EVQL_EARG, "malformed aggregate program");
       ExprPtr e = inline_inputs(lp.call, scan_out, &err);
       if (!err.empty()) return Status::error(EVQL_EARG, err);
-      // (no strings_lowerable check: a select expression never reaches the kernel -- it
+      // (no strings_refusal check: a select expression never reaches the kernel -- it
       // is evaluated once per group at emission, over the group's first row, like the
       // reference's method_call run in GroupByExpression::nextBatch; string-producing
       // functions are fine here)

@@ -129,10 +129,15 @@ typedef enum {
   EVQL_FAM_TO_INT64 = 18, /* conversion.cc:96-137  */
   EVQL_FAM_TO_TIMESTAMP64 = 19,
   /* string functions (expressions/string.cc, conversion.cc:140-215).  They PRODUCE (or
-   * read) strings and are evaluated where the reference evaluates a GROUP BY's select
-   * list: once per group, at emission (groupby.cc:187-220), on the host.  In WHERE,
-   * GROUP BY expressions and aggregate arguments they answer EVQL_ENOTSUP.  Type slot =
-   * the (first) argument's. */
+   * read) strings.  In a GROUP BY's select list they are evaluated where the reference
+   * evaluates it: once per group, at emission (groupby.cc:187-220), on the host.  In
+   * WHERE, GROUP BY expressions and the arguments of numeric aggregates of a flat scan
+   * they are evaluated per row by the kernel; a computed group key is identified by
+   * the hash of its bytes.  Still EVQL_ENOTSUP there: IF with string branches as an
+   * operand, to_string of a float64, a string as an aggregate's argument, a string
+   * value of more than 32 nodes, any of them in a nested or record scan, and a
+   * string-producing expression in a bare scan's select list.  Type slot = the (first)
+   * argument's. */
   EVQL_FAM_TO_STRING = 20,  /* to_string#string/X;  sql_tostring: NULL tag -> "NULL" */
   EVQL_FAM_CONCAT = 21,     /* concat / add#string/string;string; */
   EVQL_FAM_LCASE = 22,
