@@ -34,6 +34,11 @@ __global__ void k_table_init(TableInitArgs a) {
        i += (u64) gridDim.x * blockDim.x) {
     a.words[i] = a.identity[i % a.nwords];
   }
+  // the status words and counters of the step that begins
+  if (blockIdx.x == 0) {
+    if (a.status && threadIdx.x < 4) a.status[threadIdx.x] = 0;
+    if (a.counters && threadIdx.x < 8) a.counters[threadIdx.x] = 0;
+  }
 }
 
 __global__ void k_table_compact(const u64* words, u64 gcap, u64 stride, u32 nwords,
@@ -127,6 +132,58 @@ __global__ void __launch_bounds__(kBlock) k_table_count(const u64* words, u64 gc
     u32 t = 0;
     for (int i = 0; i < kBlock / 64; ++i) t += wsum[i];
     if (t) atomicAdd((unsigned long long*) counter, (unsigned long long) t);
+  }
+}
+
+// The epilogue of a step: k_table_count and k_table_compact in one pass, the records going
+// straight into a pinned host block (TableTailArgs).  The count is exact whatever
+// max_records is; a host that reads count > max_records ignores the records.
+__global__ void __launch_bounds__(kBlock) k_table_tail(TableTailArgs a) {
+  __shared__ u64 base_s;  // one atomic per workgroup and round, as in k_table_compact
+  __shared__ u32 last_s;
+  const u64 nslots = a.gcap + 2;
+  const u64 step = (u64) gridDim.x * blockDim.x;
+  const u64 rounds = (nslots + step - 1) / step;
+  u64* counter = (u64*) a.counters + 4;
+  u64* out = (u64*) a.block + kTailRecords;
+  for (u64 it = 0; it < rounds; ++it) {
+    const u64 s = (it * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+    const u64 k = s < nslots ? a.words[s * a.nwords] : EVQL_EMPTY;
+    const bool occ = k != EVQL_EMPTY;
+    u32 total;
+    const u32 ex = block_excl_scan(occ ? 1u : 0u, &total);
+    if (threadIdx.x == 0) {
+      base_s = total ? atomicAdd((unsigned long long*) counter, (unsigned long long) total) : 0;
+    }
+    __syncthreads();
+    const u64 idx = base_s + ex;
+    __syncthreads();
+    if (!occ || idx >= a.max_records) continue;
+    u64* rec = out + idx * (a.nwords + 1);
+    rec[0] = s == a.gcap ? 1ull : (s == a.gcap + 1 ? 2ull : 0ull);
+    rec[1] = s == a.gcap ? EVQL_EMPTY : k;
+    for (u32 w = 1; w < a.nwords; ++w) rec[1 + w] = a.words[s * a.nwords + w];
+  }
+  // the workgroup that is done last has every other one's count behind its fence
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const u64 done = atomicAdd((unsigned long long*) &a.counters[kTailDoneCounter], 1ull);
+    last_s = done + 1 == (u64) gridDim.x;
+  }
+  __syncthreads();
+  if (!last_s) return;
+  __threadfence();
+  if (threadIdx.x < 8) {
+    a.block[kTailCounters + threadIdx.x] =
+        __hip_atomic_load(&a.counters[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (threadIdx.x < 2) {
+    a.block[kTailStatus + threadIdx.x] = (u64) a.status[2 * threadIdx.x] |
+                                         ((u64) a.status[2 * threadIdx.x + 1] << 32);
+  }
+  if (threadIdx.x == 0) {
+    a.block[kTailCount] = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.block[kTailSeq] = a.seq;
   }
 }
 
@@ -2351,6 +2408,11 @@ hipError_t launch_table_compact(const uint64_t* words, uint64_t gcap, uint64_t s
   hipLaunchKernelGGL(k_table_compact, dim3(grid_for(gcap + 2)), dim3(kBlock), 0, s,
                      (const u64*) words, (u64) gcap, (u64) stride, nwords, (u64*) out_records,
                      (u64) max_records, (u64*) counter);
+  return hipGetLastError();
+}
+
+hipError_t launch_table_tail(const TableTailArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_table_tail, dim3(grid_for(a.gcap + 2)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // capi.cc -- the extern "C" surface declared in include/evql_gpu.h.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <memory>
@@ -597,6 +598,13 @@ static int create_one(evql_ctx_t* ctx, evql_table_t* table, const evql_plan_desc
   }
   q->row_begin = plan->row_begin;
   q->row_end = plan->row_end;
+  // EVQL_EAGER_TAIL=0: every step takes the lazy tail (count pass, blocking copies, compaction
+  // on the first next_batch); =records: the eager block, but result columns packed by the
+  // row interpreter (what the measurements compare the direct packer against)
+  if (const char* et = getenv("EVQL_EAGER_TAIL")) {
+    if (strcmp(et, "0") == 0) q->eager_tail = evql_query::EAGER_OFF;
+    if (strcmp(et, "records") == 0) q->eager_tail = evql_query::EAGER_RECORDS;
+  }
   if (plan->group_mode != EVQL_MODE_FINAL && plan->group_mode != EVQL_MODE_PARTIAL) {
     return fail(EVQL_EARG, "bad group mode");
   }
@@ -669,6 +677,9 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch, const evql_pl
       p->fsum_exp[k] = ex;
       p->fsum_bound[k] = b;
     }
+  }
+  if (parts.size() > 1) {
+    for (auto& p : parts) p->in_chain = true;
   }
   for (size_t i = 1; i < parts.size(); ++i) head->chain.push_back(parts[i].release());
   *out = parts[0].release();

@@ -10,6 +10,11 @@ evql_query::~evql_query() {
   if (d_status) hipFree(d_status);
   if (d_counters) hipFree(d_counters);
   if (d_small_rec) hipFree(d_small_rec);
+  if (h_tail && tail_pool) {
+    // (an epilogue that is still in flight stores to the block: it goes back idle)
+    if (launched) hipDeviceSynchronize();
+    tail_pool->give(h_tail);
+  }
   for (auto* p : d_pairset) {
     if (p) hipFree(p);
   }
@@ -44,14 +49,51 @@ namespace evql {
 // query execution
 // ---------------------------------------------------------------------------
 // an empty group table: every word of every slot at its operation's identity
-static hipError_t init_gtab(const evql_query* q, hipStream_t s) {
+// (step_prologue: the same launch zeroes the query's status words and counters)
+static hipError_t init_gtab(const evql_query* q, hipStream_t s, bool step_prologue = false) {
   const KernelPlan& kp = q->kp;
   TableInitArgs ia{};
   ia.words = q->d_gtab;
   ia.stride = q->gcap + 8;
   ia.nwords = uint32_t(kp.words_per_slot());
   slot_identities(kp, ia.nwords, ia.identity);
+  if (step_prologue) {
+    ia.status = q->d_status;
+    ia.counters = q->d_counters;
+  }
   return launch_table_init(ia, s);
+}
+
+// The eager step tail: which launches leave their groups in the pinned block, and how many.
+// Evaluated by every launch (a relaunch after a grown table asks again); everything it
+// refuses takes the lazy tail, which is what ran for every plan before.
+static const uint32_t kEagerMaxRecords = 4096;    // far below results.cc kDeviceEmitMinGroups
+static const uint64_t kEagerMaxSlots = 1u << 18;  // the epilogue scans block-wise: small tables only
+uint32_t eager_tail_records(const evql_query* q) {
+  const KernelPlan& kp = q->kp;
+  // EVQL_EAGER_TAIL=0
+  if (q->eager_tail == evql_query::EAGER_OFF) return 0;
+  // the cardinality probe aggregates several launches into one table and reads only counts
+  if (q->keep_table) return 0;
+  // a partition's file chain: the groups leave through chain_merge, not through next_batch
+  if (q->in_chain) return 0;
+  // no group table
+  if (kp.bare_scan) return 0;
+  // most groups leave the LDS tables as dense records, and there are many of them
+  if (kp.partitioned) return 0;
+  // the records are translated from dictionary codes first (query_records_view)
+  if (q->dict_key) return 0;
+  // PARTIAL rows read the pair sets; a full set is regrown and the scan re-run
+  if (kp.n_distinct > 0) return 0;
+  // first-row values are gathered from the table once the records are known (lazy path)
+  if (kp.need_first_row) return 0;
+  // ORDER BY .. LIMIT: select_top_records picks the records on the device
+  if (!q->order.empty() && q->has_limit) return 0;
+  // large tables with few groups: the count-only pass is the cheaper one there
+  if (q->gcap > kEagerMaxSlots) return 0;
+  const uint64_t rw = uint64_t(kp.words_per_slot()) + 1;
+  const uint64_t fit = (kTailBlockBytes / 8 - kTailRecords) / rw;
+  return uint32_t(std::min<uint64_t>(fit, kEagerMaxRecords));
 }
 
 static Status alloc_gtab(evql_query* q, uint64_t gcap) {
@@ -455,10 +497,13 @@ Status query_launch(evql_query* q) {
     Status st = alloc_gtab(q, cap);
     if (!st.ok()) return st;
   }
+  q->tail_valid = false;
+  q->tail_armed = 0;
+  uint32_t n_launches = 0;
   if (!q->keep_table) {
-    HIP_TRY(init_gtab(q, s));
-    HIP_TRY(hipMemsetAsync(q->d_status, 0, 16, s));
-    HIP_TRY(hipMemsetAsync(q->d_counters, 0, 64, s));
+    // one prologue: empty table, status words and counters
+    HIP_TRY(init_gtab(q, s, true));
+    ++n_launches;
   } else {
     HIP_TRY(hipMemsetAsync(q->d_counters + kFreshGroupCounter, 0, 8, s));  // (the group count is recounted)
   }
@@ -594,13 +639,41 @@ Status query_launch(evql_query* q) {
     int grid = q->grid;
     if (uint64_t(grid) > a.ntiles) grid = int(a.ntiles);
     HIP_TRY(hipModuleLaunchKernel(q->module.fn, grid, 1, 1, kp.block, 1, 1, 0, s, nullptr, config));
+    ++n_launches;
   }
   HIP_TRY(hipEventRecord(q->ev1, s));
-  // group count into counter word 4 (read back by finish together with the rest)
-  HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, uint32_t(kp.words_per_slot()),
-                               nullptr, 0, q->d_counters + kFreshGroupCounter, s));
+  const uint32_t eager = eager_tail_records(q);
+  if (eager) {
+    // one epilogue: group count, status words, counters and the records of a small result
+    // into the pinned block finish reads after its one wait
+    if (!q->h_tail) {
+      void* p = nullptr;
+      HIP_TRY(ctx->pinned->take(&p));
+      q->tail_pool = ctx->pinned;
+      q->h_tail = static_cast<uint64_t*>(p);
+      void* dp = nullptr;
+      HIP_TRY(hipHostGetDevicePointer(&dp, p, 0));
+      q->d_tail = static_cast<uint64_t*>(dp);
+    }
+    TableTailArgs ta{};
+    ta.words = q->d_gtab;
+    ta.gcap = q->gcap;
+    ta.nwords = uint32_t(kp.words_per_slot());
+    ta.max_records = eager;
+    ta.status = q->d_status;
+    ta.counters = q->d_counters;
+    ta.block = q->d_tail;
+    ta.seq = ++q->tail_seq;
+    HIP_TRY(launch_table_tail(ta, s));
+    q->tail_armed = eager;
+  } else {
+    // group count into counter word 4 (read back by finish together with the rest)
+    HIP_TRY(launch_table_compact(q->d_gtab, q->gcap, q->gcap + 8, uint32_t(kp.words_per_slot()),
+                                 nullptr, 0, q->d_counters + kFreshGroupCounter, s));
+  }
+  ++n_launches;
   q->launched = true;
-  q->stats.n_kernel_launches = 3;
+  q->stats.n_kernel_launches = n_launches;
   q->stats.rows_scanned = a.row_end - a.row_begin;
   return Status();
 }
@@ -653,7 +726,21 @@ Status query_finish(evql_query* q) {
   for (int attempt = 0; attempt < 12; ++attempt) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     uint32_t status[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(status, q->d_status, 16, hipMemcpyDeviceToHost));
+    uint64_t counters[8];
+    // the eager tail: everything is in the pinned block once the stream has drained.  (A
+    // relaunch below enqueues its own epilogue or count pass; `eager` follows it.)
+    const bool eager = q->tail_armed != 0;
+    if (eager) {
+      const uint64_t* blk = q->h_tail;
+      if (blk[kTailSeq] != q->tail_seq) {
+        return Status::error(EVQL_ERUNTIME, "step epilogue did not write its result block");
+      }
+      memcpy(status, blk + kTailStatus, 16);
+      memcpy(counters, blk + kTailCounters, 64);
+      counters[kFreshGroupCounter] = blk[kTailCount];
+    } else {
+      HIP_TRY(hipMemcpy(status, q->d_status, 16, hipMemcpyDeviceToHost));
+    }
     if (status[0] & 1u) return Status::error(EVQL_ERUNTIME, "division by zero");
     if (status[0] & 4u) return Status::error(EVQL_ERUNTIME, "modulo by zero");
     if (status[0] & 32u) {
@@ -715,8 +802,7 @@ Status query_finish(evql_query* q) {
     q->stats.kernel_ms = ms;
     // (a record scan's per-record reduction ran when the operator was built)
     q->stats.total_ms = ms + q->within_record_ms;
-    uint64_t counters[8];
-    HIP_TRY(hipMemcpy(counters, q->d_counters, 64, hipMemcpyDeviceToHost));
+    if (!eager) HIP_TRY(hipMemcpy(counters, q->d_counters, 64, hipMemcpyDeviceToHost));
     q->stats.rows_passed = counters[0];
     q->zstats.tiles_skipped = counters[5];
     if (q->reported_rows_scanned != ~0ull) q->stats.rows_scanned = q->reported_rows_scanned;
@@ -732,6 +818,9 @@ Status query_finish(evql_query* q) {
     q->executed = true;
     q->fetched = false;
     q->emit_pos = 0;
+    // more groups than the block takes: its records are ignored, the first next_batch
+    // compacts the table (results.cc collect_records)
+    q->tail_valid = eager && q->dense_n == 0 && q->ngroups <= q->tail_armed;
     return Status();
   }
   return Status::error(EVQL_ENOMEM, "group table kept overflowing");
@@ -751,6 +840,7 @@ Status query_recount(evql_query* q) {
   q->ngroups = n + q->dense_n;
   q->stats.num_groups = q->ngroups;
   q->fetched = false;
+  q->tail_valid = false;  // (the block holds the table as finish saw it)
   q->executed = true;
   q->emit_pos = 0;
   return Status();
@@ -764,6 +854,7 @@ static Status rebuild_table(evql_query* q, uint64_t total) {
   hipStream_t s = ctx->stream;
   const KernelPlan& kp = q->kp;
   const uint32_t nwords = uint32_t(kp.words_per_slot());
+  q->tail_valid = false;
   // groups already in the table (overflowed buckets of the partitioned path, or all)
   uint64_t in_table = q->ngroups - q->dense_n;
   DevBuf<uint64_t> old_rec;
@@ -885,6 +976,7 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
     return Status::error(EVQL_EARG, "a pair's group is not in the table: import the group records first");
   }
   q->fetched = false;
+  q->tail_valid = false;
   return Status();
 }
 
@@ -917,6 +1009,8 @@ Status query_reset(evql_query* q) {
   q->stats.rows_passed = 0;
   q->executed = true;
   q->fetched = false;
+  q->tail_valid = false;
+  q->tail_armed = 0;
   q->launched = false;
   q->emit_pos = 0;
   return Status();

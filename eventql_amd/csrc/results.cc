@@ -297,15 +297,8 @@ static Status select_top_records(evql_query* q, uint64_t want, FetchedRecords* r
 
 // step 3: the records on the host in a deterministic order: by first row (scan order) or
 // by identity
-static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t nwords) {
+static void sort_host_records(evql_query* q, uint64_t n, uint32_t nwords) {
   const KernelPlan& kp = q->rplan();
-  hipStream_t s = q->ctx->stream;
-  q->records.assign(n * (nwords + 1), 0);
-  if (n) {
-    HIP_TRY(hipMemcpyAsync(q->records.data(), d_rec, n * (nwords + 1) * 8,
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
   const size_t rw = nwords + 1;
   std::vector<uint64_t> idx(n);
   for (uint64_t i = 0; i < n; ++i) idx[i] = i;
@@ -321,7 +314,26 @@ static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, 
     memcpy(&sorted[i * rw], &r[idx[i] * rw], rw * 8);
   }
   q->records.swap(sorted);
+}
+
+static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t nwords) {
+  hipStream_t s = q->ctx->stream;
+  q->records.assign(n * (nwords + 1), 0);
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(q->records.data(), d_rec, n * (nwords + 1) * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  sort_host_records(q, n, nwords);
   return Status();
+}
+
+// steps 1 to 3 of an eager step tail (query_run.cc): the epilogue of the launch left the
+// records in the pinned block, finish has waited for it -- no device work here
+static void records_from_block(evql_query* q, uint64_t n, uint32_t nwords) {
+  const uint64_t* rec = q->h_tail + kTailRecords;
+  q->records.assign(rec, rec + n * (nwords + 1));
+  sort_host_records(q, n, nwords);
 }
 
 // step 4a, after an exchange: the first-row values of every scan column out of the merged
@@ -474,19 +486,36 @@ static Status fetch_distinct_sets(evql_query* q, uint64_t n, uint32_t nwords) {
 static Status fetch_results(evql_query* q) {
   const KernelPlan& kp = q->rplan();
   FetchedRecords r;
-  Status st = collect_records(q, &r);
-  if (!st.ok()) return st;
+  Status st;
   const uint64_t want = q->offset + q->limit;
-  if (r.n && !q->order.empty() && q->has_limit && want < r.n) {
-    st = select_top_records(q, want, &r);
+  // the eager step tail: every group of the table is in the pinned block already (not after
+  // a merge, an import or a recount -- they clear tail_valid --, and not where ORDER BY ..
+  // LIMIT, set after the launch, selects its records on the device)
+  const bool from_block = q->tail_valid && !q->merged &&
+                          !(!q->order.empty() && q->has_limit && want < q->stats.num_groups);
+  if (from_block) {
+    r.nwords = uint32_t(kp.words_per_slot());
+    r.n = r.total = q->stats.num_groups;
+  } else {
+    st = collect_records(q, &r);
     if (!st.ok()) return st;
+    if (r.n && !q->order.empty() && q->has_limit && want < r.n) {
+      st = select_top_records(q, want, &r);
+      if (!st.ok()) return st;
+    }
   }
   const uint64_t n = r.n;
   q->ngroups = n;
   q->rec_stride = r.nwords + 1;
   q->demit.active = false;
   EmitArgs ea{};
-  if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea)) {
+  if (from_block) {
+    // (plans that read first rows or count distinct values never arm the block)
+    records_from_block(q, n, r.nwords);
+    q->first_vals.clear();
+    q->first_tags.clear();
+    q->distinct_values.clear();
+  } else if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea)) {
     st = emit_on_device(q, ea, r.d_rec, n, r.nwords);
     if (!st.ok()) return st;
     q->records.clear();
@@ -872,6 +901,72 @@ static Status order_fetched(evql_query* q) {
   return Status();
 }
 
+// Select lists made of the group key and plain aggregate reads in EVQL_MODE_FINAL without
+// ORDER BY / LIMIT -- what device_emit_columns recognises, less the first-row columns -- are
+// packed straight from the fetched record words: no Value, no eval_expr, no vector per row.
+// Everything else (post-aggregate arithmetic, exact sums, strings, PARTIAL rows) keeps the
+// row loop of query_next_batch.
+static bool direct_pack_columns(const evql_query* q, EmitArgs* ea) {
+  if (q->eager_tail != evql_query::EAGER_ON) return false;
+  // (with first rows the row loop also evaluates the scan select list, which can raise)
+  if (q->rplan().need_first_row) return false;
+  if (!device_emit_columns(q, q->merged, ea)) return false;
+  for (uint32_t i = 0; i < ea->ncols; ++i) {
+    if (ea->col[i].kind == 2) return false;
+  }
+  return true;
+}
+
+// byte for byte what select_value / agg_value + append_svector write for these columns
+static void pack_direct(evql_query* q, const EmitArgs& ea, size_t max_rows, evql_column_buf_t* cols,
+                        size_t* nrows) {
+  const size_t rw = q->rec_stride;
+  const uint64_t m = std::min<uint64_t>(q->ngroups - q->emit_pos, max_rows);
+  const uint64_t* rec0 = m ? &q->records[q->emit_pos * rw] : nullptr;
+  q->out_cols.resize(ea.ncols);
+  for (uint32_t i = 0; i < ea.ncols; ++i) {
+    const EmitCol& e = ea.col[i];
+    std::vector<uint8_t>& out = q->out_cols[i];
+    out.resize(size_t(m) * e.elem);  // (keeps its capacity from batch to batch)
+    uint8_t* p = out.data();
+    for (uint64_t g = 0; g < m; ++g, p += e.elem) {
+      const uint64_t* rec = rec0 + g * rw;
+      uint64_t bits;
+      uint8_t tag = 0;
+      if (e.kind == 0) {
+        const bool null_key = rec[0] == 2;
+        bits = null_key ? 0 : rec[1];
+        tag = null_key ? uint8_t(EVQL_STAG_NULL) : uint8_t(0);
+      } else {
+        bits = rec[e.word];
+        if (e.count_word >= 0) {  // min / max / mean: NULL without a non-NULL input
+          const uint64_t cnt = rec[e.count_word];
+          if (cnt == 0) {
+            bits = 0;
+            tag = EVQL_STAG_NULL;
+          } else if (e.is_mean) {
+            double sum;
+            memcpy(&sum, &bits, 8);
+            const double mean = sum / double(cnt);
+            memcpy(&bits, &mean, 8);
+          }
+        }
+      }
+      if (e.elem == 2) {
+        p[0] = bits ? 1 : 0;
+        p[1] = tag;
+      } else {
+        memcpy(p, &bits, 8);
+        p[8] = tag;
+      }
+    }
+    cols[i].data = out.data();
+    cols[i].size = out.size();
+  }
+  q->emit_pos += m;
+  *nrows = size_t(m);
+}
+
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows) {
   if (q->kp.bare_scan) return bare_next_batch(q, max_rows, cols, nrows);
   if (!q->executed) return Status::error(EVQL_EARG, "execute() was not called");
@@ -899,6 +994,13 @@ Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols,
     q->emit_pos += m;
     *nrows = size_t(m);
     return Status();
+  }
+  {
+    EmitArgs ea{};
+    if (direct_pack_columns(q, &ea)) {
+      pack_direct(q, ea, max_rows, cols, nrows);
+      return Status();
+    }
   }
   const KernelPlan& kp = q->rplan();
   const size_t nsel = q->select.size();

@@ -97,6 +97,30 @@ struct KernelCacheStats {
   double compile_ms = 0;
 };
 
+// Pinned host blocks of one size that the device stores to (the eager step tail,
+// query_run.cc): taken by an operator on first use, handed back when it closes -- an
+// operator per step (config 5w) then pays no hipHostMalloc.  Shared by the context and the
+// operators that hold a block, so that it outlives whichever is destroyed first.
+static const size_t kTailBlockBytes = 256 << 10;
+struct PinnedPool {
+  std::vector<void*> free_blocks;
+  PinnedPool() = default;
+  PinnedPool(const PinnedPool&) = delete;
+  PinnedPool& operator=(const PinnedPool&) = delete;
+  ~PinnedPool() {
+    for (void* p : free_blocks) hipHostFree(p);
+  }
+  hipError_t take(void** out) {
+    if (!free_blocks.empty()) {
+      *out = free_blocks.back();
+      free_blocks.pop_back();
+      return hipSuccess;
+    }
+    return hipHostMalloc(out, kTailBlockBytes, hipHostMallocDefault);
+  }
+  void give(void* p) { free_blocks.push_back(p); }
+};
+
 }  // namespace evql
 
 struct evql_ctx {
@@ -106,6 +130,7 @@ struct evql_ctx {
   int num_cus = 256;
   std::map<std::string, evql::Module> modules;  // by source fingerprint
   evql::KernelCacheStats kstats;
+  std::shared_ptr<evql::PinnedPool> pinned = std::make_shared<evql::PinnedPool>();
 };
 
 namespace evql {
@@ -364,6 +389,19 @@ struct evql_query {
   uint32_t* d_status = nullptr;
   uint64_t* d_counters = nullptr;
   uint64_t* d_small_rec = nullptr;  // 1 MiB: dense records of small results
+  // The eager step tail (query_run.cc eager_tail_records): behind the scan one
+  // epilogue kernel leaves status words, counters, group count and -- for small results --
+  // the group records themselves in a pinned host block; finish waits once and reads it,
+  // next_batch packs from it without touching the device.
+  enum EagerTail { EAGER_OFF = 0, EAGER_RECORDS = 1, EAGER_ON = 2 };
+  int eager_tail = EAGER_ON;    // EVQL_EAGER_TAIL, read when the operator is created
+  bool in_chain = false;        // one table of a partition's file chain (merged by chain_merge)
+  std::shared_ptr<evql::PinnedPool> tail_pool;  // where h_tail came from and goes back to
+  uint64_t* h_tail = nullptr;   // the block (host address)
+  uint64_t* d_tail = nullptr;   // the block as the device addresses it
+  uint64_t tail_seq = 0;        // stamp of the last epilogue enqueued
+  uint32_t tail_armed = 0;      // records the enqueued epilogue may write (0: lazy tail enqueued)
+  bool tail_valid = false;      // the block holds ALL groups of the table as finish saw it
   // count_distinct pair sets (3 word planes of pairset_cap slots each)
   uint64_t* d_pairset[4] = {nullptr, nullptr, nullptr, nullptr};
   uint64_t pairset_cap = 0;
@@ -560,6 +598,9 @@ Status query_dense_into_table(evql_query* q);
 Status query_reserve_groups(evql_query* q, uint64_t extra);
 Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, uint64_t n);
 void fill_host_args(evql_query* q, HostArgs* ap);
+// how many group records the epilogue of the next launch may leave in the pinned block;
+// 0: the lazy tail runs (count pass, blocking copies, compaction on the first next_batch)
+uint32_t eager_tail_records(const evql_query* q);
 
 // bare_scan.cc: the life cycle of a bare-scan query (kp.bare_scan)
 void bare_configure(evql_query* q);
