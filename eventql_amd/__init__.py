@@ -138,6 +138,7 @@ def lib():
                                           C.POINTER(C.c_void_p)]
     L.evql_lsm_chain_build.argtypes = [C.c_void_p]
     L.evql_lsm_chain_filter.argtypes = [C.c_void_p, C.c_int, C.POINTER(_u8p), _u64p, _u64p]
+    K.bind_chain_compact(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_destroy.argtypes = [C.c_void_p]
     L.evql_merge_add_frame.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -520,6 +521,7 @@ class LsmChain:
     def __init__(self, ctx):
         self.ctx = ctx
         self.tables = []
+        self.compact_stats = None
         self.h = C.c_void_p()
         _check(lib().evql_lsm_chain_create(ctx.h, C.byref(self.h)))
 
@@ -554,6 +556,24 @@ class LsmChain:
         q = C.c_void_p()
         _check(lib().evql_query_create_chain(self.ctx.h, self.h, C.byref(plan.desc), C.byref(q)))
         return Query(self, plan, q)
+
+    def compact(self, specs, row_order=K.COMPACT_SCAN_ORDER, page_order=K.PAGE_ORDER_COLUMNS):
+        """evql_lsm_chain_compact: the rows the chain's filters keep as ONE resident Table
+        (closed by the caller); `specs` as for Writer, looked up by name in every table.
+        row_order: capi.COMPACT_SCAN_ORDER (newest table first) / COMPACT_FILE_ORDER (oldest
+        first).  The chain stays usable; compact_stats holds the last call's figures."""
+        names = [c["name"].encode() for c in specs]
+        cs = (K.ColumnSpec * max(1, len(specs)))()
+        for i, c in enumerate(specs):
+            cs[i] = K.ColumnSpec(names[i], c["logical_type"], c["storage_type"],
+                                 c.get("column_id", i + 1), c.get("rlevel_max", 0),
+                                 c.get("dlevel_max", 0), c.get("bitpack_max_value", 0))
+        t = C.c_void_p()
+        st = K.CompactStats()
+        _check(lib().evql_lsm_chain_compact(self.h, cs, len(specs), row_order, page_order,
+                                            C.byref(t), C.byref(st)))
+        self.compact_stats = {f[0]: getattr(st, f[0]) for f in K.CompactStats._fields_}
+        return Table(self.ctx, t)
 
     def close(self):
         if self.h:

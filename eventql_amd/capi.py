@@ -221,5 +221,23 @@ class Transport(C.Structure):
                 ("all_to_all_words", ALL_TO_ALL_FN), ("name", C.c_char_p)]
 
 PAGE_ORDER_COLUMNS, PAGE_ORDER_ROWS = 0, 1
+
+# evql_compact_order_t
+COMPACT_SCAN_ORDER, COMPACT_FILE_ORDER = 0, 1
+
+
+class CompactStats(C.Structure):
+    """evql_compact_stats_t"""
+    _fields_ = [("rows_in", C.c_uint64), ("rows_written", C.c_uint64),
+                ("string_bytes", C.c_uint64), ("n_tables", C.c_uint32),
+                ("n_kernel_launches", C.c_uint32), ("n_host_waits", C.c_uint32),
+                ("gather_ms", C.c_float), ("encode_ms", C.c_float)]
+
+
+def bind_chain_compact(lib):
+    """declares evql_lsm_chain_compact on the loaded library"""
+    lib.evql_lsm_chain_compact.restype = C.c_int
+    lib.evql_lsm_chain_compact.argtypes = [C.c_void_p, C.POINTER(ColumnSpec), C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(C.c_void_p), C.POINTER(CompactStats)]
 FLOAT_SUM_FAST = 0
 FLOAT_SUM_EXACT = 1

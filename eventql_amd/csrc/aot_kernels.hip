@@ -1783,6 +1783,223 @@ __global__ void __launch_bounds__(kBlock) k_filter_expand(const u8* levels, cons
   }
 }
 
+// ---- compaction of a partition file chain (chain_compact.cc) --------------------------------
+// The kept rows (slots) of every table move to consecutive positions of SoA output columns.
+// A workgroup owns one 2048-row tile; where the tile's kept rows go was fixed by a scan
+// of the per-tile counts, and a row's rank inside its tile is recomputed from the filter
+// words (popcounts), so no per-row rank array passes through HBM, no atomic decides a
+// position and no workgroup waits for another.  Consecutive lanes take consecutive rows.
+
+// filter word w (< ceil(nrows / 64)) of a table: NULL bits = every row is kept; the bits of
+// the last word behind nrows are masked, whatever they hold
+__device__ __forceinline__ u64 cmp_filter_word(const uint64_t* bits, u64 nrows, u64 w) {
+  u64 m = bits ? bits[w] : ~0ull;
+  const u64 left = nrows - w * 64;
+  if (left < 64) m &= (1ull << left) - 1;
+  return m;
+}
+
+// kept rows per tile: 32 lanes reduce the popcounts of a tile's 32 filter words
+__global__ void __launch_bounds__(kBlock) k_cmp_ranks(const uint64_t* __restrict__ bits, u64 nrows,
+                                                      uint64_t* __restrict__ tile_counts) {
+  const u64 w = (u64) blockIdx.x * kBlock + threadIdx.x;
+  const u64 nwords = (nrows + 63) / 64;
+  u32 c = w < nwords ? (u32) __popcll(cmp_filter_word(bits, nrows, w)) : 0u;
+#pragma unroll
+  for (int d = 16; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);  // (stays inside 32 lanes)
+  if ((threadIdx.x & 31) == 0 && w < nwords) tile_counts[w >> 5] = c;
+}
+
+__global__ void __launch_bounds__(kBlock) k_cmp_fixed(CmpFixedArgs a) {
+  constexpr u32 kWords = kDecodeTile / 64, kWaves = kBlock / 64, kChunks = kDecodeTile / kBlock;
+  __shared__ u64 s_word[kWords];
+  __shared__ u32 s_before[kWords];  // kept rows of the tile in front of word i
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 tile = blockIdx.x;
+  const u64 nwords = (a.nrows + 63) / 64;
+  if (tid < kWords) {
+    const u64 w = tile * kWords + tid;
+    s_word[tid] = w < nwords ? cmp_filter_word(a.bits, a.nrows, w) : 0ull;
+  }
+  __syncthreads();
+  if (tid < kWords) {
+    u32 p = 0;
+    for (u32 i = 0; i < tid; ++i) p += (u32) __popcll(s_word[i]);
+    s_before[tid] = p;
+  }
+  __syncthreads();
+  const u64 dst0 = a.tile_off[tile];
+  const u64 below = (1ull << lane) - 1;
+  for (u32 c = 0; c < a.ncols; ++c) {
+    const CmpFixedCol col = a.cols[c];
+#pragma unroll
+    for (u32 k = 0; k < kChunks; ++k) {
+      const u64 word = s_word[k * kWaves + wave];
+      if (!((word >> lane) & 1)) continue;
+      const u64 row = tile * kDecodeTile + (u64) k * kBlock + tid;
+      const u64 dst = dst0 + s_before[k * kWaves + wave] + (u32) __popcll(word & below);
+      if (dst >= a.out_cap) continue;
+      col.out_vals[dst] = rt_column_value(a.image, col.src, row);
+      if (col.out_nulls) col.out_nulls[dst] = col.src.tags ? (col.src.tags[row] & 1) : 0;
+    }
+  }
+}
+
+// Repeated / nested columns: a slot is kept iff its record's filter bit is set; its record =
+// records started in front of the tile (rec_offsets) + level-0 slots of the tile up to and
+// including it - 1 (k_filter_expand's scheme: a ballot per 64 slots).  kWrite = false counts
+// the kept slots of the tile, kWrite = true moves (r, d, value) to tile_off[tile] + rank.
+// Without rlevels a record has one slot; without dlevels / values (a column the table does
+// not have) that slot is (d = 0, no value).  All threads reach the barriers.
+template <bool kWrite>
+__device__ __forceinline__ void cmp_slots_tile(const CmpSlotArgs& a) {
+  constexpr u32 kWaves = kBlock / 64, kChunks = kDecodeTile / kBlock;
+  __shared__ u32 s_start[kChunks * kWaves], s_keep[kChunks * kWaves];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u64 tile = blockIdx.x;
+  const u64 base = tile * kDecodeTile;
+  u64 starts[kChunks], keeps[kChunks];
+#pragma unroll
+  for (u32 j = 0; j < kChunks; ++j) {
+    const u64 s = base + (u64) j * kBlock + tid;
+    starts[j] = __ballot(s < a.nslots && (!a.rlevels || a.rlevels[s] == 0));
+    if (lane == 0) s_start[j * kWaves + wave] = (u32) __popcll(starts[j]);
+  }
+  __syncthreads();
+  const u64 rec0 = a.rlevels ? a.rec_offsets[tile] : base;
+  const u64 upto = (2ull << lane) - 1;  // lanes <= this one
+  u32 before = 0;
+#pragma unroll
+  for (u32 j = 0; j < kChunks; ++j) {
+    u32 in_row = 0, row_total = 0;
+#pragma unroll
+    for (u32 w = 0; w < kWaves; ++w) {
+      const u32 c = s_start[j * kWaves + w];
+      in_row += w < wave ? c : 0;
+      row_total += c;
+    }
+    const u64 s = base + (u64) j * kBlock + tid;
+    const u64 started = rec0 + before + in_row + (u32) __popcll(starts[j] & upto);
+    bool keep = false;
+    if (s < a.nslots && started > 0) {
+      const u64 rec = started - 1;
+      keep = rec < a.nrec && (!a.bits || ((a.bits[rec >> 6] >> (rec & 63)) & 1));
+    }
+    keeps[j] = __ballot(keep);
+    if (lane == 0) s_keep[j * kWaves + wave] = (u32) __popcll(keeps[j]);
+    before += row_total;
+  }
+  __syncthreads();
+  if (!kWrite) {
+    if (tid == 0) {
+      u32 total = 0;
+      for (u32 i = 0; i < kChunks * kWaves; ++i) total += s_keep[i];
+      a.tile_counts[tile] = total;
+    }
+    return;
+  }
+  const u64 dst0 = a.tile_off[tile];
+  u32 kept_before = 0;
+#pragma unroll
+  for (u32 j = 0; j < kChunks; ++j) {
+    u32 in_row = 0, row_total = 0;
+#pragma unroll
+    for (u32 w = 0; w < kWaves; ++w) {
+      const u32 c = s_keep[j * kWaves + w];
+      in_row += w < wave ? c : 0;
+      row_total += c;
+    }
+    if ((keeps[j] >> lane) & 1) {
+      const u64 s = base + (u64) j * kBlock + tid;
+      const u64 dst = dst0 + kept_before + in_row + (u32) __popcll(keeps[j] & (upto >> 1));
+      if (dst < a.out_cap) {
+        if (a.out_r) a.out_r[dst] = a.rlevels ? a.rlevels[s] : 0;
+        a.out_d[dst] = a.dlevels ? a.dlevels[s] : 0;
+        a.out_vals[dst] = a.values ? a.values[s] : 0;
+      }
+    }
+    kept_before += row_total;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_cmp_slot_counts(CmpSlotArgs a) { cmp_slots_tile<false>(a); }
+__global__ void __launch_bounds__(kBlock) k_cmp_slots(CmpSlotArgs a) { cmp_slots_tile<true>(a); }
+
+// exclusive scan of one u64 per thread across a 256-thread block; *total out
+__device__ __forceinline__ u64 block_excl_scan_u64(u64 v, u64* total) {
+  __shared__ u64 wsum64[kBlock / 64];
+  u64 incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    u32 lo = (u32) incl, hi = (u32) (incl >> 32);
+    lo = __shfl_up(lo, d, 64);
+    hi = __shfl_up(hi, d, 64);
+    if ((int) (threadIdx.x & 63) >= d) incl += (u64) lo | ((u64) hi << 32);
+  }
+  const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 63) wsum64[wave] = incl;
+  __syncthreads();
+  u64 off = 0, tot = 0;
+  for (u32 w = 0; w < kBlock / 64; ++w) {
+    if (w < wave) off += wsum64[w];
+    tot += wsum64[w];
+  }
+  *total = tot;
+  return off + incl - v;
+}
+
+// Strings: the gathered words of one table's segment are (len << 40) | position in that
+// table's page stream (0 for NULL / undefined slots: no bytes).  Bytes per 2048-word tile,
+// then -- tile sums scanned across all segments of the column -- the bytes into the column's
+// heap as one run per tile; the words become (len << 40) | heap offset.
+__global__ void __launch_bounds__(kBlock) k_cmp_str_sizes(CmpStrArgs a) {
+  const u64 i0 = (u64) blockIdx.x * kDecodeTile + (u64) threadIdx.x * 8;
+  u64 bytes = 0;
+#pragma unroll
+  for (u32 k = 0; k < 8; ++k) bytes += i0 + k < a.n ? a.words[i0 + k] >> 40 : 0ull;
+  u64 total;
+  block_excl_scan_u64(bytes, &total);
+  if (threadIdx.x == 0) a.tile_sums[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kBlock) k_cmp_str_bytes(CmpStrArgs a) {
+  const u64 i0 = (u64) blockIdx.x * kDecodeTile + (u64) threadIdx.x * 8;
+  u64 bytes = 0;
+#pragma unroll
+  for (u32 k = 0; k < 8; ++k) bytes += i0 + k < a.n ? a.words[i0 + k] >> 40 : 0ull;
+  // where every string of the tile ends among the tile's bytes, and where its bytes come from
+  __shared__ u64 s_end[kDecodeTile], s_src[kDecodeTile];
+  u64 total;
+  u64 rel = block_excl_scan_u64(bytes, &total);
+  const u64 tile_pos = a.tile_off[blockIdx.x];
+#pragma unroll
+  for (u32 k = 0; k < 8; ++k) {
+    const bool valid = i0 + k < a.n;
+    const u64 sp = valid ? a.words[i0 + k] : 0ull;
+    const u64 len = sp >> 40;
+    s_src[threadIdx.x * 8 + k] = sp & kStrOffMask;
+    if (valid) a.words[i0 + k] = (len << 40) | (tile_pos + rel);
+    rel += len;
+    s_end[threadIdx.x * 8 + k] = rel;
+  }
+  __syncthreads();
+  // the tile's bytes are one run of the heap: consecutive lanes copy consecutive bytes, each
+  // finds its string by bisection over the ends (a byte outside the stream or the heap is
+  // not copied)
+  for (u64 j = threadIdx.x; j < total; j += kBlock) {
+    u32 lo = 0, hi = kDecodeTile - 1;
+    while (lo < hi) {
+      const u32 mid = (lo + hi) >> 1;
+      if (s_end[mid] > j) hi = mid; else lo = mid + 1;
+    }
+    const u64 src = s_src[lo] + (j - (lo ? s_end[lo - 1] : 0ull));
+    if (src < a.src_bytes && tile_pos + j < a.heap_cap) {
+      a.heap[tile_pos + j] = vbyte_fwd(a.image, (const u64*) a.pages, src);
+    }
+  }
+}
+
 // ---- nested scans over sibling repeated groups ---------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_record_starts(const u8* levels, const u64* tile_offsets,
                                                           u64 nslots, u64* starts, u64 max_starts) {
@@ -3377,6 +3594,50 @@ hipError_t launch_wr_str_emit(uint8_t* image, const uint64_t* pages, const uint6
   hipLaunchKernelGGL(k_wr_str_emit, dim3((unsigned) ntiles), dim3(kBlock), 0, s, image,
                      (const u64*) pages, (const u64*) dense, (u64) n, (const u64*) chunk_offsets,
                      heap);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_ranks(const uint64_t* bits, uint64_t nrows, uint64_t* tile_counts,
+                            hipStream_t s) {
+  const u64 nwords = (nrows + 63) / 64;
+  if (nwords == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_ranks, dim3((unsigned) ((nwords + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     bits, (u64) nrows, tile_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_fixed(const CmpFixedArgs& a, hipStream_t s) {
+  const u64 ntiles = (a.nrows + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0 || a.ncols == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_fixed, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_slot_counts(const CmpSlotArgs& a, hipStream_t s) {
+  const u64 ntiles = (a.nslots + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_slot_counts, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_slots(const CmpSlotArgs& a, hipStream_t s) {
+  const u64 ntiles = (a.nslots + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_slots, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_str_sizes(const CmpStrArgs& a, hipStream_t s) {
+  const u64 ntiles = (a.n + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_str_sizes, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_str_bytes(const CmpStrArgs& a, hipStream_t s) {
+  const u64 ntiles = (a.n + kDecodeTile - 1) / kDecodeTile;
+  if (ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_str_bytes, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -430,6 +430,21 @@ int evql_table_generate(evql_ctx_t* ctx, const evql_synth_spec_t* spec, evql_tab
 }
 
 // ---- device-side writer -----------------------------------------------------------------
+static ColumnSpec column_spec_of(const evql_column_spec_t& c) {
+  ColumnSpec cs;
+  cs.name = c.name;
+  cs.logical_type = ColumnType(c.logical_type);
+  cs.storage_type = ColumnEncoding(c.storage_type);
+  cs.column_id = c.column_id;
+  cs.rlevel_max = c.rlevel_max;
+  cs.dlevel_max = c.dlevel_max;
+  cs.bitpack_max_value = c.bitpack_max_value;
+  if (cs.bitpack_max_value == 0) {
+    cs.bitpack_max_value = cs.storage_type == ColumnEncoding::BOOLEAN_BITPACKED ? 1u : 0xffffffffu;
+  }
+  return cs;
+}
+
 int evql_table_from_device_columns(evql_ctx_t* ctx, const evql_column_spec_t* cols, int ncols,
                                    const evql_device_column_t* data, uint64_t num_rows,
                                    evql_table_t** out) {
@@ -450,19 +465,7 @@ int evql_table_from_device_columns_ordered(evql_ctx_t* ctx, const evql_column_sp
   std::vector<ColumnSpec> specs;
   std::vector<DeviceColumnIn> in;
   for (int i = 0; i < ncols; ++i) {
-    ColumnSpec cs;
-    cs.name = cols[i].name;
-    cs.logical_type = ColumnType(cols[i].logical_type);
-    cs.storage_type = ColumnEncoding(cols[i].storage_type);
-    cs.column_id = cols[i].column_id;
-    cs.rlevel_max = cols[i].rlevel_max;
-    cs.dlevel_max = cols[i].dlevel_max;
-    cs.bitpack_max_value = cols[i].bitpack_max_value;
-    if (cs.bitpack_max_value == 0) {
-      cs.bitpack_max_value =
-          cs.storage_type == ColumnEncoding::BOOLEAN_BITPACKED ? 1u : 0xffffffffu;
-    }
-    specs.push_back(cs);
+    specs.push_back(column_spec_of(cols[i]));
     in.push_back({data[i].values, data[i].nulls, data[i].bytes, data[i].rlevels, data[i].dlevels,
                   data[i].num_slots});
   }
@@ -479,19 +482,7 @@ int evql_writer_create(const evql_column_spec_t* cols, int ncols, evql_writer_t*
   API_TRY
   std::unique_ptr<evql_writer> w(new evql_writer());
   for (int i = 0; i < ncols; ++i) {
-    ColumnSpec cs;
-    cs.name = cols[i].name;
-    cs.logical_type = ColumnType(cols[i].logical_type);
-    cs.storage_type = ColumnEncoding(cols[i].storage_type);
-    cs.column_id = cols[i].column_id;
-    cs.rlevel_max = cols[i].rlevel_max;
-    cs.dlevel_max = cols[i].dlevel_max;
-    cs.bitpack_max_value = cols[i].bitpack_max_value;
-    if (cs.bitpack_max_value == 0) {
-      cs.bitpack_max_value =
-          cs.storage_type == ColumnEncoding::BOOLEAN_BITPACKED ? 1u : 0xffffffffu;
-    }
-    w->specs.push_back(cs);
+    w->specs.push_back(column_spec_of(cols[i]));
   }
   w->w.reset(new TableWriter(w->specs));
   *out = w.release();
@@ -683,6 +674,31 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch, const evql_pl
   }
   for (size_t i = 1; i < parts.size(); ++i) head->chain.push_back(parts[i].release());
   *out = parts[0].release();
+  return EVQL_OK;
+  API_CATCH
+}
+
+int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                           int row_order, int page_order, evql_table_t** out,
+                           evql_compact_stats_t* stats) {
+  API_TRY
+  if (!ch || !cols || !out || ncols <= 0) return fail(EVQL_EARG, "bad arguments");
+  if (row_order != EVQL_COMPACT_SCAN_ORDER && row_order != EVQL_COMPACT_FILE_ORDER) {
+    return fail(EVQL_EARG, "bad row order");
+  }
+  if (page_order != EVQL_PAGE_ORDER_COLUMNS && page_order != EVQL_PAGE_ORDER_ROWS) {
+    return fail(EVQL_EARG, "bad page order");
+  }
+  std::vector<ColumnSpec> specs;
+  for (int i = 0; i < ncols; ++i) {
+    if (!cols[i].name) return fail(EVQL_EARG, "output column without a name");
+    specs.push_back(column_spec_of(cols[i]));
+  }
+  if (hipSetDevice(lsm_chain_ctx(ch)->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  evql_table* t = nullptr;
+  Status st = chain_compact(ch, specs, row_order, page_order, &t, stats);
+  if (!st.ok()) return ret(st);
+  *out = t;
   return EVQL_OK;
   API_CATCH
 }

@@ -232,4 +232,8 @@ size_t lsm_chain_parts(const evql_lsm_chain* ch, std::vector<evql_table*>* table
   return tables->size();
 }
 evql_ctx* lsm_chain_ctx(const evql_lsm_chain* ch) { return ch ? ch->ctx : nullptr; }
+void lsm_chain_rows_kept(const evql_lsm_chain* ch, std::vector<uint64_t>* kept) {
+  kept->clear();
+  for (const auto& e : ch->entries) kept->push_back(e.kept);
+}
 }  // namespace evql

@@ -147,6 +147,67 @@ static Status exact_slot_count(evql_table* t, int li, uint64_t* out) {
   return Status();
 }
 
+Status nested_column_slots(evql_table* t, int li, ColumnSlots* out) {
+  const ColumnLayout& c = t->layout.columns[li];
+  hipStream_t s = t->ctx->stream;
+  const uint64_t nrec = t->layout.num_rows;
+  *out = ColumnSlots();
+  out->nslots = nrec;
+  if (c.rlevel_max > 0) {
+    uint32_t rbits = 0;
+    Status st = stream_bits(t, c.rlevel_pages, &rbits);
+    if (!st.ok()) return st;
+    if (rbits == 0) return Status::error(EVQL_ENOTSUP, "repeated column without repetition levels");
+    const uint64_t cap = level_stream_capacity(c.rlevel_pages, rbits);
+    auto hit = t->leaf_cache.find(li);
+    if (hit != t->leaf_cache.end()) {
+      out->rlevels = hit->second.levels;
+      out->rec_offsets = hit->second.rec_offsets;
+    } else {
+      const uint64_t capp = padded_rows(cap);
+      const uint64_t ntiles = (cap + kDecodeTile - 1) / kDecodeTile;
+      HIP_TRY(out->rlevels_owned.alloc(capp));
+      HIP_TRY(hipMemsetAsync(out->rlevels_owned, 0xff, capp, s));
+      HIP_TRY(out->rec_offsets_owned.alloc((ntiles + 2) * 8));
+      const uint32_t thr0 = 0;
+      st = decode_levels(t, li, 1, rbits, cap, out->rlevels_owned, 1, &thr0, &out->rec_offsets_owned);
+      if (!st.ok()) return st;
+      out->rlevels = out->rlevels_owned;
+      out->rec_offsets = out->rec_offsets_owned;
+    }
+    // number of real slots = start of record number `nrec` (the stream is zero-padded)
+    DevBuf<uint64_t> d_n;
+    HIP_TRY(d_n.alloc(8));
+    uint64_t n = cap;
+    HIP_TRY(hipMemcpyAsync(d_n, &n, 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_find_nth(out->rlevels, out->rec_offsets, cap, 0, nrec, d_n, s));
+    HIP_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->nslots = n;
+  }
+  if (c.dlevel_max > 0) {
+    uint32_t dbits = 0;
+    Status st = stream_bits(t, c.dlevel_pages, &dbits);
+    if (!st.ok()) return st;
+    const uint64_t cap = dbits ? level_stream_capacity(c.dlevel_pages, dbits) : out->nslots;
+    if (cap < out->nslots) return Status::error(EVQL_EIO, "end of column reached: " + c.name);
+    const uint64_t capp = padded_rows(cap);
+    HIP_TRY(out->dlevels_owned.alloc(capp));
+    HIP_TRY(hipMemsetAsync(out->dlevels_owned, dbits ? 0xff : 0, capp, s));
+    if (dbits) {
+      st = decode_levels(t, li, 2, dbits, cap, out->dlevels_owned, 0, nullptr, nullptr);
+      if (!st.ok()) return st;
+    }
+    out->dlevels = out->dlevels_owned;
+  }
+  uint64_t vcap = 0;
+  Status st = nested_slot_values(t, li, out->nslots, &out->values_owned, &vcap);
+  if (!st.ok()) return st;
+  if (vcap < out->nslots) return Status::error(EVQL_EIO, "end of column reached: " + c.name);
+  out->values = out->values_owned;
+  return Status();
+}
+
 // flattens `cols` (all of one ancestor chain) to one value per leaf slot:
 // (*flat)[i] is borrowed from the table's nested cache
 Status materialize_nested(evql_query* q, const std::vector<ColAccess>& cols,

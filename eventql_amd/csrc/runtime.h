@@ -572,6 +572,20 @@ Status materialize_nested_zip(evql_query* q, const std::vector<ColAccess>& cols,
 Status materialize_within_record(evql_query* q);
 Status expand_record_filter(evql_query* q, const LeafLevels* leaf);
 Status apply_where_resets(evql_query* q, const LeafLevels* leaf);
+// A repeated / nested column as the device writer takes one (chain_compact.cc): levels as one
+// byte per slot, one value word per slot (0 where d != dlevel_max; strings: len << 40 |
+// position).  The repetition levels are borrowed from the table's leaf cache where it has
+// them, everything else is owned; all arrays are padded to a tile multiple.
+struct ColumnSlots {
+  uint64_t nslots = 0;
+  const uint8_t* rlevels = nullptr;       // NULL: rlevel_max == 0, one slot per record
+  const uint64_t* rec_offsets = nullptr;  // scanned per-tile counts of the level-0 slots
+  const uint8_t* dlevels = nullptr;
+  const uint64_t* values = nullptr;
+  DevBuf<uint8_t> rlevels_owned, dlevels_owned;
+  DevBuf<uint64_t> rec_offsets_owned, values_owned;
+};
+Status nested_column_slots(evql_table* t, int li, ColumnSlots* out);
 
 // zone_maps.cc
 // the (cached) zone statistics of flat column `name`; EVQL_EARG when it does not qualify
@@ -620,6 +634,11 @@ Status chain_merge(evql_query* head);
 size_t lsm_chain_parts(const evql_lsm_chain* ch, std::vector<evql_table*>* tables,
                        std::vector<const uint8_t*>* d_filters);
 evql_ctx* lsm_chain_ctx(const evql_lsm_chain* ch);
+// rows every table's filter keeps (all of them where it has none), in chain order
+void lsm_chain_rows_kept(const evql_lsm_chain* ch, std::vector<uint64_t>* kept);
+// chain_compact.cc: evql_lsm_chain_compact
+Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, int row_order,
+                     int page_order, evql_table** out, evql_compact_stats_t* stats);
 // the query's groups as dense records of rplan()'s layout: `dense` holds the first `nd`
 // groups, the remaining ngroups - nd sit in the HBM group table (compact them from there)
 struct RecordsView {

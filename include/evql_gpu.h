@@ -875,6 +875,61 @@ int evql_lsm_chain_filter(evql_lsm_chain_t* ch, int idx,
 int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch,
                             const evql_plan_desc_t* plan, evql_query_t** out);
 
+/*
+ * Compaction of a partition on the device: the rows the chain's filters keep, written as
+ * ONE cstable (SimpleCompactionStrategy::compact, db/compaction_strategy.cc:44-222: every
+ * input table read column by column, the surviving rows appended to a CSTableWriter).  The
+ * kept rows of every table are gathered into SoA columns in HBM and encoded by the device
+ * writer (evql_table_from_device_columns_ordered; `page_order` is handed to it unchanged).
+ * `ch` must be built (EVQL_EARG otherwise), is not changed and stays usable.  *out is a
+ * resident table like any other -- queries, evql_table_download_image, _write_file -- and is
+ * closed by the caller.
+ *
+ * Which rows: exactly those the chain's filters keep (evql_lsm_chain_filter); a table
+ * without a filter keeps every row; arenas take part like files.  This is PartitionCursor's
+ * visibility rule.  It is NOT the `.idx` version rule of compaction_strategy.cc:150
+ * (`version != vmap[id]`): that one needs LSMTableIndex, which this library does not restate,
+ * and nobody has shown that the two rules select the same rows on a consistent partition.
+ *
+ * Output column c (`cols[c]`), looked up by name in every table of the chain:
+ *   present         logical type, rlevel_max and dlevel_max must equal the spec's (EVQL_EARG);
+ *                   the values are decoded and re-encoded, so the storage encoding may differ
+ *                   from table to table and from the output's.  A value the output encoding
+ *                   cannot hold is treated as evql_table_from_device_columns treats it.
+ *                   FLOAT_IEEE754 words are copied bit for bit (NaN payloads, -0.0, subnormals).
+ *   absent,         one NULL per kept record of that table; for a repeated / nested column
+ *   dlevel_max >= 1 one slot (r = 0, d = 0): writeNull(0, 0), compaction_strategy.cc:171-173
+ *   absent,         EVQL_EARG "can't merge CSTables after a new required column was added"
+ *   dlevel_max == 0 (:113-117)
+ *   __lsm_is_update false for every row, whatever the tables hold (:161)
+ *   __lsm_skip      EVQL_EARG: a compacted table has no skiplist
+ * Null arguments, ncols <= 0, a bad row_order or page_order: EVQL_EARG.
+ *
+ * Not offered: the `.idx` file next to the table, a binding in the reference-side adapter, a
+ * compaction across ranks.
+ */
+typedef enum {
+  EVQL_COMPACT_SCAN_ORDER = 0, /* tables in chain order (newest first), rows ascending:
+                                  the order PartitionCursor hands rows to the operator */
+  EVQL_COMPACT_FILE_ORDER = 1  /* tables in reverse chain order (oldest first), rows ascending:
+                                  the order compaction_strategy.cc:82 walks its input */
+} evql_compact_order_t;
+
+typedef struct {
+  uint64_t rows_in;        /* records of all tables of the chain */
+  uint64_t rows_written;   /* records the filters keep */
+  uint64_t string_bytes;   /* bytes of all gathered string heaps */
+  uint32_t n_tables;
+  uint32_t n_kernel_launches; /* of the gather (ranks, scans, k_cmp_*), without the writer's */
+  uint32_t n_host_waits;   /* of the gather: 1, + 1 when there is a STRING column */
+  float gather_ms;         /* device time, chain columns -> SoA */
+  float encode_ms;         /* device time of the writer */
+} evql_compact_stats_t;
+
+int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                           int row_order, int page_order,
+                           evql_table_t** out, evql_compact_stats_t* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* build support                                                              */
 /* ------------------------------------------------------------------------ */
