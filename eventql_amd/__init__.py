@@ -69,6 +69,8 @@ def lib():
     L.evql_table_image_size.argtypes = [C.c_void_p]
     L.evql_table_device_bytes.restype = C.c_uint64
     L.evql_table_device_bytes.argtypes = [C.c_void_p]
+    L.evql_table_narrow_float_passes.restype = C.c_uint64
+    L.evql_table_narrow_float_passes.argtypes = [C.c_void_p]
     L.evql_table_zone_map.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
     L.evql_table_download_image.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
@@ -367,6 +369,11 @@ class Table:
         narrow copies, dictionaries, flattened nested columns)"""
         return lib().evql_table_device_bytes(self.h)
 
+    def narrow_float_passes(self):
+        """passes run so far that tried to keep a FLOAT_IEEE754 column once more as float32
+        (one per column: a copy or a remembered refusal)"""
+        return lib().evql_table_narrow_float_passes(self.h)
+
     def zone_map(self, name):
         """evql_table_zone_map: (zmin, zmax) of every 2048 rows of column `name` as numpy
         uint64 arrays; built on first use and cached on the table"""
@@ -633,7 +640,8 @@ def compile_only(plan, columns, cache_dir=None):
     """compile the fused kernel of `plan` for gfx950 without a device.
     columns: list of dict(name, logical_type, storage_type, dlevel_max=0, bits=0,
     narrow_bits=0); bits = width of a bit-packed file column, narrow_bits = 8 / 16 / 32: a
-    required UINT64_PLAIN / LEB128 column as read from the flat narrow copy a table keeps"""
+    required UINT64_PLAIN / LEB128 column as read from the flat narrow copy a table keeps;
+    narrow_bits = 32 on a required FLOAT_IEEE754 column: as read from its float32 copy"""
     infos = (K.ColumnInfo * len(columns))()
     for i, c in enumerate(columns):
         infos[i].name = c["name"].encode()

@@ -81,3 +81,8 @@ def precompile_all():
               if c["storage_type"] == K.ENC_UINT64_PLAIN else c for c in PLAIN_COLUMNS]
     for p in (config2(), config3(), config4()):
         compile_only(p, narrow)
+    # ... and with v read from its float32 copy: the synthetic v = (x >> 40) / 1024 has 24
+    # significant bits, so a table of benchmark size keeps one (EVQL_NARROW_FLOAT)
+    narrow_f = [dict(c, narrow_bits=32) if c["name"] == "v" else c for c in narrow]
+    for p in (config2(), config3(), config4()):
+        compile_only(p, narrow_f)

@@ -3219,6 +3219,58 @@ __global__ void __launch_bounds__(kBlock) k_narrow_flat(const u8* image, const u
   }
 }
 
+// float32 bits of the double `x` when x is exactly a float32 zero, normal number, infinity or
+// quiet NaN -- (double)(float) x has the bits of x and (float) x is no denormal; false
+// otherwise.  Decided on the bits, so no rounding or denormal mode of the compilation enters:
+// the low 29 mantissa bits must be clear, and the exponent lie in float32's normal range
+// (a signalling NaN would come back quiet: refused).
+__device__ __forceinline__ bool f64_as_exact_f32(u64 x, u32* f) {
+  const u32 sign = (u32) (x >> 63) << 31;
+  const u32 e = (u32) (x >> 52) & 0x7ffu;
+  const u64 m = x & 0xfffffffffffffull;
+  if (e == 0 && m == 0) {
+    *f = sign;
+    return true;
+  }
+  if (m & 0x1fffffffull) return false;
+  const u32 m23 = (u32) (m >> 29);
+  if (e == 0x7ffu) {
+    if (m23 != 0 && !(m23 & 0x400000u)) return false;
+    *f = sign | 0x7f800000u | m23;
+    return true;
+  }
+  if (e < 1023u - 126u || e > 1023u + 127u) return false;
+  *f = sign | ((e - 896u) << 23) | m23;
+  return true;
+}
+
+// The float32 copy (evql_f32_x2) of a required FLOAT_IEEE754 column of the image, in the
+// layout k_narrow_flat writes at 32 bits: rows r, r + 1 (r even) from one 16-byte load, one
+// 8-byte store; a zero behind an odd n.  A value that is not exactly float32 sets *refused
+// (the host then drops the copy); workgroups stop once they see it set.
+__global__ void __launch_bounds__(kBlock) k_narrow_f32(const u8* image, const u64* src_pages,
+                                                       u8* dst, u64 n, u32* refused) {
+  const u64 npairs = (n + 1) / 2;
+  for (u64 pi = (u64) blockIdx.x * kBlock + threadIdx.x; pi < npairs; pi += (u64) gridDim.x * kBlock) {
+    if (__hip_atomic_load(refused, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    const u64 r = 2 * pi;
+    const u8* p = image + evql_page(src_pages, r / kPlain64PageValues) + ((r % kPlain64PageValues) << 3);
+    const evql_u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x4*>(p));
+    u32 f0 = 0, f1 = 0;
+    bool ok = f64_as_exact_f32((u64) q.x | ((u64) q.y << 32), &f0);
+    if (r + 1 < n) ok = f64_as_exact_f32((u64) q.z | ((u64) q.w << 32), &f1) && ok;
+    if (!ok) {
+      atomicOr(refused, 1u);
+      return;
+    }
+    typedef u32 u32x2n __attribute__((ext_vector_type(2)));
+    u32x2n o;
+    o.x = f0;
+    o.y = f1;
+    *reinterpret_cast<u32x2n*>(dst + 8 * pi) = o;
+  }
+}
+
 // UInt64PageWriter / UInt32PageWriter: value i at stream byte i * width
 __global__ void __launch_bounds__(kBlock) k_wr_plain(u8* image, const u64* pages,
                                                      const u64* dense, u64 n, u32 width) {
@@ -3523,6 +3575,14 @@ hipError_t launch_narrow_flat(const uint8_t* image, const uint64_t* src_pages,
   hipLaunchKernelGGL(k_narrow_flat, dim3(grid_for((n + 1) / 2, kBlock, 65536)), dim3(kBlock), 0, s,
                      (const u8*) image, (const u64*) src_pages, (const u64*) values, (u8*) dst,
                      (u64) n, (u32) bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_narrow_f32(const uint8_t* image, const uint64_t* src_pages, uint8_t* dst,
+                             uint64_t n, uint32_t* refused, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_narrow_f32, dim3(grid_for((n + 1) / 2, kBlock, 65536)), dim3(kBlock), 0, s,
+                     (const u8*) image, (const u64*) src_pages, (u8*) dst, (u64) n, (u32*) refused);
   return hipGetLastError();
 }
 

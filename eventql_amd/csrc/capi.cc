@@ -200,6 +200,8 @@ uint64_t evql_table_device_bytes(const evql_table_t* t) {
   return total;
 }
 
+uint64_t evql_table_narrow_float_passes(const evql_table_t* t) { return t->narrow_float_passes; }
+
 int evql_table_zone_map(evql_table_t* t, const char* column, uint64_t* zmin, uint64_t* zmax,
                         size_t cap, size_t* n) {
   API_TRY
@@ -1051,6 +1053,13 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
                  ColumnEncoding(ci.storage_type) == ColumnEncoding::UINT64_LEB128))) {
       c.mode = ColAccess::NARROW;
       c.bits = w;
+      c.packed = true;
+    } else if (w == 32 && ci.dlevel_max == 0 && ci.rlevel_max == 0 && c.mode == ColAccess::PLAIN64 &&
+               c.stype == EVQL_T_FLOAT64 && !c.from_uint_to_float &&
+               ColumnEncoding(ci.storage_type) == ColumnEncoding::FLOAT_IEEE754) {
+      // the float32 copy of a FLOAT_IEEE754 column (narrow_float_column)
+      c.mode = ColAccess::NARROW_F32;
+      c.bits = 32;
       c.packed = true;
     }
   }

@@ -12,7 +12,10 @@ namespace evql {
 // how the fused kernel reads one scan column
 struct ColAccess {
   // NARROW: the table's flat narrow copy of a LEB128 / PLAIN integer column (bits = 8 / 16 / 32)
-  enum Mode { PLAIN64 = 0, PLAIN32 = 1, BITPACKED = 2, SOA = 3, NARROW = 4 };
+  // NARROW_F32: the table's flat float32 copy of a FLOAT_IEEE754 column whose values are all
+  // exactly float32 (bits = 32, packed); widened back to the file's 64 bits by the accessor.
+  // Only the tile loops read it: row-addressed readers (RtColumn) keep the file's pages.
+  enum Mode { PLAIN64 = 0, PLAIN32 = 1, BITPACKED = 2, SOA = 3, NARROW = 4, NARROW_F32 = 5 };
   std::string name;
   uint32_t stype = EVQL_T_NIL;  // evql_stype seen by the VM
   Mode mode = PLAIN64;
@@ -22,7 +25,7 @@ struct ColAccess {
   bool from_uint_to_float = false;  // FLOAT64 stype over a uint column: (double) u
   bool string_hash = false;   // STRING column materialised as hash64
   bool string_bytes = false;  // ... and compared bytewise on the device (strpos array)
-  bool packed = false;        // NARROW: read from the narrow copy, not from the file's pages
+  bool packed = false;        // NARROW / NARROW_F32: read from the copy, not from the file's pages
   bool dict_code = false;     // PLAIN32 over the table's dictionary codes of a STRING column
   int layout_index = -1;      // index into TableLayout::columns
 };

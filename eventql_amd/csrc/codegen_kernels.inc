@@ -357,6 +357,10 @@ struct Gen {
           s << ind << "  evql_bitpacked_x2<" << c.bits << ">(A.col[" << i << "].base, r, x" << i
             << "[u][0], x" << i << "[u][1]);\n";
           break;
+        case ColAccess::NARROW_F32:
+          s << ind << "  evql_f32_x2(A.col[" << i << "].base, r, x" << i << "[u][0], x" << i
+            << "[u][1]);\n";
+          break;
         case ColAccess::SOA:
           s << ind << "  evql_soa_x2(A.col[" << i << "].soa, r, x" << i << "[u][0], x" << i
             << "[u][1]);\n";

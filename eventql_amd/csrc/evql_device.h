@@ -307,6 +307,24 @@ __device__ __forceinline__ void evql_narrow_x2(const u8* base, u64 r, u64& v0, u
   v1 = evql_opaque(b);
 }
 
+// The float32 copy the runtime keeps of a FLOAT64 column whose every value is exactly a zero,
+// normal, infinite or quiet-NaN float32 (table.cc narrow_float_column): the layout of a
+// 32-bit narrow copy, holding float32 bits.  Rows r, r + 1 (r even) are one non-temporal
+// 8-byte load; widening is exact, so the row function sees the 64 bits the file holds.
+// (Not evql_opaque: that hides integer ranges, and these are doubles.)  The empty asm pins
+// the two conversions behind the load, for every row: left free, the compiler sinks them into
+// the branch of the rows that pass WHERE, a load whose rows all fail is then never waited
+// for, and the next tile's address arithmetic needs an s_waitcnt vmcnt in the middle of its
+// loads before it may reuse that load's registers (seen in config 3's evql_scan_agg).
+__device__ __forceinline__ void evql_f32_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+  typedef u32 evql_u32x2n __attribute__((ext_vector_type(2)));
+  const evql_u32x2n q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2n*>(base + (r << 2)));
+  double d0 = (double) __uint_as_float(q.x), d1 = (double) __uint_as_float(q.y);
+  asm("" : "+v"(d0), "+v"(d1));
+  v0 = (u64) __double_as_longlong(d0);
+  v1 = (u64) __double_as_longlong(d1);
+}
+
 // What the generated text calls: it names a column's accessor by its width whether the bits
 // lie in libsimdcomp pages of the file (base, pages, i) or in a flat narrow copy (base, i).
 template <int B>

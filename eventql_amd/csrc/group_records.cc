@@ -76,6 +76,12 @@ Status first_row_columns(evql_query* q, std::vector<RtColumn>* out) {
     rc.pages = ca.layout_index >= 0 ? t->d_pages[ca.layout_index][0] : nullptr;
     rc.mode = ca.mode;
     rc.bits = ca.bits;
+    if (ca.mode == ColAccess::NARROW_F32) {
+      // a float32 copy serves the tile loads only: a single row comes from the file's pages
+      rc.mode = ColAccess::PLAIN64;
+      rc.bits = 0;
+      continue;
+    }
     if (q->nested) {
       if (ca.packed) {
         rc.pages = nullptr;

@@ -244,9 +244,28 @@ Status query_prepare(evql_query* q) {
           hit = t->materialized.find(c.name);
         }
       }
-      if (hit != t->materialized.end() && hit->second.packed_bits) {
+      if (hit != t->materialized.end() && hit->second.packed_bits && !hit->second.packed_f32) {
         c.mode = ColAccess::NARROW;
         c.bits = hit->second.packed_bits;
+        c.packed = true;
+        repacked = true;
+      }
+    } else if (c.mode == ColAccess::PLAIN64 && cl.storage_type == ColumnEncoding::FLOAT_IEEE754 &&
+               cl.dlevel_max == 0 && cl.rlevel_max == 0 && c.stype == EVQL_T_FLOAT64 &&
+               !c.from_uint_to_float && t->layout.num_rows >= t->narrow_float_min_rows) {
+      // A required FLOAT_IEEE754 column whose every value is exactly float32: kept once more
+      // as a flat float32 array that the tile loads widen back -- 4 bytes per
+      // row for the same 64 bits.  The first operator that references the column runs the
+      // pass; a refusal is remembered on the table.
+      auto hit = t->materialized.find(c.name);
+      if (hit == t->materialized.end()) {
+        Status st = narrow_float_column(t, c.layout_index);
+        if (!st.ok()) return st;
+        hit = t->materialized.find(c.name);
+      }
+      if (hit != t->materialized.end() && hit->second.packed_f32) {
+        c.mode = ColAccess::NARROW_F32;
+        c.bits = 32;
         c.packed = true;
         repacked = true;
       }

@@ -7,6 +7,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 #include "aot_kernels.h"
@@ -178,6 +179,11 @@ struct MaterializedColumn {
   // then reads 1 - 4 bytes per value instead of an 8-byte SoA word
   uint8_t* d_packed = nullptr;
   uint32_t packed_bits = 0;
+  // d_packed holds float32 bits, not unsigned integers: the copy of a required FLOAT_IEEE754
+  // column whose values are all exactly float32 (table.cc narrow_float_column, packed_bits =
+  // 32).  Only the fused kernels' tile loads read it (evql_f32_x2); integer readers of
+  // packed_bits (evql_narrow_rt) must skip such an entry.
+  bool packed_f32 = false;
   bool string_hash = false;
   // strings: (len << 40) | byte position of the value in the column's page stream,
   // per row (bytewise compares in the fused kernel, result emission)
@@ -194,6 +200,7 @@ struct MaterializedColumn {
     std::swap(string_hash, o.string_hash);
     std::swap(d_packed, o.d_packed);
     std::swap(packed_bits, o.packed_bits);
+    std::swap(packed_f32, o.packed_f32);
     return *this;
   }
   ~MaterializedColumn() {
@@ -250,6 +257,12 @@ struct evql_table {
   std::map<std::string, ZoneMap> zone_maps;
   // required UINT64_PLAIN columns are kept narrow from this many rows on (~0 = never)
   uint64_t narrow_min_rows;
+  // required FLOAT_IEEE754 columns are tried as float32 copies from this many rows on (~0 =
+  // never); the columns a pass refused (some value is not exactly float32), so that no
+  // later operator repeats it; and the passes run so far
+  uint64_t narrow_float_min_rows;
+  std::set<std::string> narrow_float_refused;
+  uint64_t narrow_float_passes = 0;
   // nested scans: column flattened to one value per output row of the scans whose
   // deepest repeated column is `leaf` -- key (column, leaf) layout indices.  Like
   // `materialized`, decoded once per table and shared by every operator.
@@ -559,6 +572,11 @@ Status pack_narrow(hipStream_t s, const uint64_t* d_values, uint64_t n, DevBuf<u
 static const uint64_t kNarrowMinRows = 1ull << 26;
 uint64_t narrow_plain_min_rows();
 Status narrow_plain_column(evql_table* t, int li, uint64_t maxv);
+// Required FLOAT_IEEE754 columns kept once more as float32 where every value
+// is exactly a float32 zero, normal, infinity or quiet NaN: in tables of at least
+// kNarrowMinRows rows (EVQL_NARROW_FLOAT overrides; EVQL_NARROW_PLAIN=0 turns it off too).
+uint64_t narrow_float_min_rows();
+Status narrow_float_column(evql_table* t, int li);
 Status materialize_column(evql_table* t, const ColAccess& ca);
 
 // nested.cc: the scans of a nested query, run by query_prepare

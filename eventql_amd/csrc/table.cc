@@ -110,7 +110,9 @@ Status table_from_image(evql_ctx* ctx, const void* image, size_t len, bool keep_
 
 }  // namespace evql
 
-evql_table::evql_table() : narrow_min_rows(evql::narrow_plain_min_rows()) {}
+evql_table::evql_table()
+    : narrow_min_rows(evql::narrow_plain_min_rows()),
+      narrow_float_min_rows(evql::narrow_float_min_rows()) {}
 
 evql_table::~evql_table() {
   if (d_image) hipFree(d_image);
@@ -287,6 +289,58 @@ Status narrow_plain_column(evql_table* t, int li, uint64_t maxv) {
   HIP_TRY(hipStreamSynchronize(s));
   m.d_packed = d_packed.release();
   m.packed_bits = bits;
+  t->materialized[c.name] = std::move(m);
+  return Status();
+}
+
+// EVQL_NARROW_FLOAT: 0 = FLOAT_IEEE754 columns are never kept as float32, N = in tables of at
+// least N rows.  EVQL_NARROW_PLAIN=0 ("the file's own pages") turns these copies off as
+// well; any other value of it leaves this threshold alone.
+uint64_t narrow_float_min_rows() {
+  if (narrow_plain_min_rows() == ~0ull) return ~0ull;
+  if (const char* e = getenv("EVQL_NARROW_FLOAT")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end != e) return v == 0 ? ~0ull : v;  // 0 = off
+  }
+  return kNarrowMinRows;
+}
+
+// Required FLOAT_IEEE754 column `li` once more as float32 -- t->materialized[name] with
+// packed_bits = 32 and packed_f32 -- when every value is exactly a float32 zero, normal
+// number, infinity or quiet NaN (k_narrow_f32): widening gives back the file's 64 bits, so
+// the fused kernel streams 4 bytes per row for the same result.  One pass, one host wait.
+// A column with any other value is remembered in t->narrow_float_refused and keeps its
+// pages.  The file's own pages stay either way (row-addressed readers use them).
+Status narrow_float_column(evql_table* t, int li) {
+  const ColumnLayout& c = t->layout.columns[li];
+  const uint64_t n = t->layout.num_rows;
+  if (t->materialized.count(c.name) || t->narrow_float_refused.count(c.name) || n == 0) return Status();
+  if (n > uint64_t(c.data_pages.size()) * (kPlainPageSize / 8)) return Status();  // (short file)
+  hipStream_t s = t->ctx->stream;
+  const uint64_t bytes = narrow_copy_bytes(n, 32);
+  DevBuf<uint8_t> d_packed;
+  DevBuf<uint32_t> d_refused;
+  HIP_TRY(d_packed.alloc(bytes));
+  HIP_TRY(d_refused.alloc(4));
+  // zero behind the value pairs the kernel writes, then the maximum word of a 32-bit copy
+  const uint64_t written = (n + 1) / 2 * 8;
+  HIP_TRY(hipMemsetAsync(d_packed.p + written, 0, bytes - written, s));
+  HIP_TRY(hipMemsetAsync(d_packed.p + narrow_copy_max_word_at(n, 32), 0xff, 4, s));
+  HIP_TRY(hipMemsetAsync(d_refused.p, 0, 4, s));
+  HIP_TRY(launch_narrow_f32(t->d_image, t->d_pages[li][0], d_packed.p, n, d_refused.p, s));
+  uint32_t refused = 0;
+  HIP_TRY(hipMemcpyAsync(&refused, d_refused.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  ++t->narrow_float_passes;
+  if (refused) {
+    t->narrow_float_refused.insert(c.name);
+    return Status();  // (d_packed is freed here)
+  }
+  MaterializedColumn m;
+  m.d_packed = d_packed.release();
+  m.packed_bits = 32;
+  m.packed_f32 = true;
   t->materialized[c.name] = std::move(m);
   return Status();
 }

@@ -89,6 +89,9 @@ Status column_abs_max(evql_query* q, size_t i, double* out) {
     rc.mode = ColAccess::SOA;  // (the 8-byte words stay beside a packed copy)
     rc.soa = q->nested_flat[i];
     n = q->nested_rows;
+  } else if (c.mode == ColAccess::NARROW_F32) {
+    rc.mode = ColAccess::PLAIN64;  // (the file's pages hold the same values)
+    rc.bits = 0;
   } else if (c.packed) {
     const MaterializedColumn& m = t->materialized[c.name];
     rc.pages = nullptr;  // (a flat array: ColAccess::NARROW)

@@ -32,7 +32,7 @@ Status table_zone_map(evql_table* t, const std::string& name, const evql_table::
   if (rc.mode == uint32_t(ColAccess::PLAIN64)) {
     // a PLAIN column the table keeps a narrow copy of is read from the copy
     auto m = t->materialized.find(name);
-    if (m != t->materialized.end() && m->second.packed_bits) {
+    if (m != t->materialized.end() && m->second.packed_bits && !m->second.packed_f32) {
       rc.mode = uint32_t(ColAccess::NARROW);
       rc.bits = m->second.packed_bits;
       rc.pages = nullptr;

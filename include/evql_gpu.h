@@ -269,9 +269,13 @@ uint64_t evql_table_image_size(const evql_table_t* t);
 int evql_table_download_image(const evql_table_t* t, void* dst, uint64_t len);
 /* Bytes of HBM the table holds at this moment: the image with its page tables plus
  * everything cached on it since -- decoded columns, the narrow copies of LEB128 and
- * PLAIN integer columns, string dictionaries, flattened nested columns.  Grows as
- * operators touch new columns; what a memory budget should count, not the file size. */
+ * PLAIN integer columns, the float32 copies of FLOAT_IEEE754 columns, string dictionaries,
+ * flattened nested columns.  Grows as operators touch new columns; what a memory budget
+ * should count, not the file size. */
 uint64_t evql_table_device_bytes(const evql_table_t* t);
+/* Passes run so far that tried to keep a required FLOAT_IEEE754 column once more as
+ * float32 (EVQL_NARROW_FLOAT): one per column, whether it gave a copy or a refusal. */
+uint64_t evql_table_narrow_float_passes(const evql_table_t* t);
 
 /* Zone map of a flat column: the unsigned minimum and maximum of every 2048 rows (zones
  * aligned to row 0; the last one may be partial).  Built on the device on first use --
