@@ -141,6 +141,7 @@ def lib():
     L.evql_lsm_chain_build.argtypes = [C.c_void_p]
     L.evql_lsm_chain_filter.argtypes = [C.c_void_p, C.c_int, C.POINTER(_u8p), _u64p, _u64p]
     K.bind_chain_compact(L)
+    K.bind_chain_compact_sorted(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_destroy.argtypes = [C.c_void_p]
     L.evql_merge_add_frame.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -529,6 +530,7 @@ class LsmChain:
         self.ctx = ctx
         self.tables = []
         self.compact_stats = None
+        self.compact_sort_stats = None
         self.h = C.c_void_p()
         _check(lib().evql_lsm_chain_create(ctx.h, C.byref(self.h)))
 
@@ -569,17 +571,40 @@ class LsmChain:
         (closed by the caller); `specs` as for Writer, looked up by name in every table.
         row_order: capi.COMPACT_SCAN_ORDER (newest table first) / COMPACT_FILE_ORDER (oldest
         first).  The chain stays usable; compact_stats holds the last call's figures."""
-        names = [c["name"].encode() for c in specs]
-        cs = (K.ColumnSpec * max(1, len(specs)))()
-        for i, c in enumerate(specs):
-            cs[i] = K.ColumnSpec(names[i], c["logical_type"], c["storage_type"],
-                                 c.get("column_id", i + 1), c.get("rlevel_max", 0),
-                                 c.get("dlevel_max", 0), c.get("bitpack_max_value", 0))
+        cs, _names = self._column_specs(specs)
         t = C.c_void_p()
         st = K.CompactStats()
         _check(lib().evql_lsm_chain_compact(self.h, cs, len(specs), row_order, page_order,
                                             C.byref(t), C.byref(st)))
         self.compact_stats = {f[0]: getattr(st, f[0]) for f in K.CompactStats._fields_}
+        return Table(self.ctx, t)
+
+    @staticmethod
+    def _column_specs(specs):
+        names = [c["name"].encode() for c in specs]  # (kept alive by the caller)
+        cs = (K.ColumnSpec * max(1, len(specs)))()
+        for i, c in enumerate(specs):
+            cs[i] = K.ColumnSpec(names[i], c["logical_type"], c["storage_type"],
+                                 c.get("column_id", i + 1), c.get("rlevel_max", 0),
+                                 c.get("dlevel_max", 0), c.get("bitpack_max_value", 0))
+        return cs, names
+
+    def compact_sorted(self, specs, key, row_order=K.COMPACT_SCAN_ORDER,
+                       page_order=K.PAGE_ORDER_COLUMNS):
+        """evql_lsm_chain_compact_sorted: the rows compact() writes, stably sorted ascending
+        by the unsigned integer / datetime column `key` (one of `specs`, flat and required);
+        rows with equal keys keep the order compact(specs, row_order) gives them.
+        compact_stats is filled as by compact(), compact_sort_stats holds the sort's figures
+        (presorted, passes, key_min / key_max, sort_ms, permute_ms ...)."""
+        cs, _names = self._column_specs(specs)
+        t = C.c_void_p()
+        st = K.CompactStats()
+        ss = K.CompactSortStats()
+        _check(lib().evql_lsm_chain_compact_sorted(
+            self.h, cs, len(specs), None if key is None else key.encode(), row_order, page_order,
+            C.byref(t), C.byref(st), C.byref(ss)))
+        self.compact_stats = {f[0]: getattr(st, f[0]) for f in K.CompactStats._fields_}
+        self.compact_sort_stats = {f[0]: getattr(ss, f[0]) for f in K.CompactSortStats._fields_}
         return Table(self.ctx, t)
 
     def close(self):

@@ -239,5 +239,25 @@ def bind_chain_compact(lib):
     lib.evql_lsm_chain_compact.restype = C.c_int
     lib.evql_lsm_chain_compact.argtypes = [C.c_void_p, C.POINTER(ColumnSpec), C.c_int, C.c_int,
                                            C.c_int, C.POINTER(C.c_void_p), C.POINTER(CompactStats)]
+
+
+# pairs per workgroup of the k_sort_* kernels (kSortTile, csrc/aot_kernels.h)
+COMPACT_SORT_TILE = 2048
+
+
+class CompactSortStats(C.Structure):
+    """evql_compact_sort_stats_t"""
+    _fields_ = [("rows", C.c_uint64), ("key_min", C.c_uint64), ("key_max", C.c_uint64),
+                ("presorted", C.c_uint32), ("passes", C.c_uint32),
+                ("n_kernel_launches", C.c_uint32), ("n_host_waits", C.c_uint32),
+                ("sort_ms", C.c_float), ("permute_ms", C.c_float)]
+
+
+def bind_chain_compact_sorted(lib):
+    """declares evql_lsm_chain_compact_sorted on the loaded library"""
+    lib.evql_lsm_chain_compact_sorted.restype = C.c_int
+    lib.evql_lsm_chain_compact_sorted.argtypes = [
+        C.c_void_p, C.POINTER(ColumnSpec), C.c_int, C.c_char_p, C.c_int, C.c_int,
+        C.POINTER(C.c_void_p), C.POINTER(CompactStats), C.POINTER(CompactSortStats)]
 FLOAT_SUM_FAST = 0
 FLOAT_SUM_EXACT = 1

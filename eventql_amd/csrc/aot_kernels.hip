@@ -2000,6 +2000,194 @@ __global__ void __launch_bounds__(kBlock) k_cmp_str_bytes(CmpStrArgs a) {
   }
 }
 
+// ---- sorted compaction: stable LSD radix sort of (key, row) pairs -----------------------------
+// Wave w of a tile's workgroup owns the tile's pairs [w * 512, (w + 1) * 512) and walks them in
+// chunks of 64, lane l taking pair 64 * j + l: consecutive lanes on consecutive addresses, and
+// the order (wave, chunk, lane) IS the row order.  A pair's rank among the tile's earlier pairs
+// with the same digit = the wave's running count of the digit (s_cnt[wave][digit], LDS, touched
+// by that wave alone) + the lanes below it that hold the digit (eight ballots, one per bit).
+constexpr u32 kSortWaves = kBlock / 64, kSortPerWave = kSortTile / kSortWaves,
+              kSortChunks = kSortPerWave / 64;
+static_assert(kBlock == 256, "one thread per digit value");
+
+__device__ __forceinline__ u32 sort_digit(u64 key, u64 kmin, u32 shift) {
+  return (u32) ((key - kmin) >> shift) & 255u;
+}
+
+// pairs of the wave's earlier rows with digit d; cnt = the wave's 256 running counts.  Called
+// by all 64 lanes; a lane without a pair (valid = false) is nobody's peer and counts nothing.
+__device__ __forceinline__ u32 sort_wave_rank(u32 d, bool valid, u32* cnt, u32 lane) {
+  u64 peers = __ballot(valid);
+#pragma unroll
+  for (u32 b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1;
+    const u64 m = __ballot(bit);
+    peers &= bit ? m : ~m;
+  }
+  const u64 below = peers & ((1ull << lane) - 1);
+  const u32 before = cnt[d];
+  __builtin_amdgcn_wave_barrier();  // (every lane has read before the digit's first lane writes)
+  if (valid && below == 0) cnt[d] = before + (u32) __popcll(peers);
+  __builtin_amdgcn_wave_barrier();
+  return before + (u32) __popcll(below);
+}
+
+// min (as max of ~key), max and descents of the gathered key words: one streaming pass; the
+// word in front of a lane's own is the neighbour lane's (the same cache line but for one in 16)
+__global__ void __launch_bounds__(kBlock) k_sort_key_stats(const u64* __restrict__ keys, u64 n,
+                                                           u64* stats) {
+  __shared__ u64 s_red[3][kBlock / 64];
+  u64 inv = 0, mx = 0, desc = 0;
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < n; i += (u64) gridDim.x * kBlock) {
+    const u64 k = keys[i];
+    const u64 p = i ? keys[i - 1] : k;
+    inv = ~k > inv ? ~k : inv;
+    mx = k > mx ? k : mx;
+    desc += k < p ? 1 : 0;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const u64 a = shfl_xor_u64(inv, d), b = shfl_xor_u64(mx, d);
+    inv = a > inv ? a : inv;
+    mx = b > mx ? b : mx;
+    desc += shfl_xor_u64(desc, d);
+  }
+  const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+    s_red[0][wave] = inv;
+    s_red[1][wave] = mx;
+    s_red[2][wave] = desc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (u32 w = 1; w < kBlock / 64; ++w) {
+      inv = s_red[0][w] > inv ? s_red[0][w] : inv;
+      mx = s_red[1][w] > mx ? s_red[1][w] : mx;
+      desc += s_red[2][w];
+    }
+    // (max and sum commute: the three words do not depend on the order of the workgroups)
+    atomicMax((unsigned long long*) &stats[0], (unsigned long long) inv);
+    atomicMax((unsigned long long*) &stats[1], (unsigned long long) mx);
+    if (desc) atomicAdd((unsigned long long*) &stats[2], (unsigned long long) desc);
+  }
+}
+
+// hist[digit][tile] = pairs of the tile with that digit
+__global__ void __launch_bounds__(kBlock) k_sort_hist(SortPassArgs a) {
+  __shared__ u32 s_cnt[kSortWaves][256];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (u32 w = 0; w < kSortWaves; ++w) s_cnt[w][tid] = 0;
+  __syncthreads();
+  const u64 first = (u64) blockIdx.x * kSortTile + (u64) wave * kSortPerWave + lane;
+#pragma unroll
+  for (u32 j = 0; j < kSortChunks; ++j) {
+    const u64 i = first + (u64) j * 64;
+    const bool valid = i < a.n;
+    const u32 d = valid ? sort_digit(a.keys_in[i], a.kmin, a.shift) : 0u;
+    sort_wave_rank(d, valid, s_cnt[wave], lane);
+  }
+  __syncthreads();
+  u32 c = 0;
+#pragma unroll
+  for (u32 w = 0; w < kSortWaves; ++w) c += s_cnt[w][tid];
+  a.hist[(u64) tid * a.ntiles + blockIdx.x] = c;
+}
+
+// one workgroup per digit: the counts of its tiles -> pairs of the digit in earlier tiles
+__global__ void __launch_bounds__(kBlock) k_sort_digit_scan(u32* hist, u32 ntiles, u32* totals) {
+  u32* row = hist + (u64) blockIdx.x * ntiles;
+  u32 carry = 0;
+  for (u32 base = 0; base < ntiles; base += kBlock) {
+    const u32 i = base + threadIdx.x;
+    const u32 v = i < ntiles ? row[i] : 0u;
+    u32 total;
+    const u32 ex = block_excl_scan(v, &total);
+    if (i < ntiles) row[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+// The tile's pairs in digit order through LDS, then every digit's run to its place: the run of
+// (digit, tile) starts at [pairs of smaller digits] + [pairs of the digit in earlier tiles].
+__global__ void __launch_bounds__(kBlock) k_sort_scatter(SortPassArgs a) {
+  __shared__ u32 s_cnt[kSortWaves][256];  // counts, then first LDS slot of (wave, digit)
+  __shared__ u64 s_gbase[256];            // output position of the digit's run - its LDS slot
+  __shared__ u64 s_key[kSortTile];
+  __shared__ u32 s_idx[kSortTile];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (u32 w = 0; w < kSortWaves; ++w) s_cnt[w][tid] = 0;
+  __syncthreads();
+  const u64 first = (u64) blockIdx.x * kSortTile + (u64) wave * kSortPerWave + lane;
+  u64 key[kSortChunks];
+  u32 rank[kSortChunks];
+#pragma unroll
+  for (u32 j = 0; j < kSortChunks; ++j) {
+    const u64 i = first + (u64) j * 64;
+    const bool valid = i < a.n;
+    key[j] = valid ? a.keys_in[i] : 0ull;
+    rank[j] = sort_wave_rank(valid ? sort_digit(key[j], a.kmin, a.shift) : 0u, valid, s_cnt[wave], lane);
+  }
+  __syncthreads();
+  // thread d places digit d (it alone touches column d of s_cnt)
+  u32 c[kSortWaves], mine = 0;
+#pragma unroll
+  for (u32 w = 0; w < kSortWaves; ++w) {
+    c[w] = s_cnt[w][tid];
+    mine += c[w];
+  }
+  u32 tile_pairs;
+  const u32 slot = block_excl_scan(mine, &tile_pairs);
+  u64 all_pairs;
+  const u64 smaller = block_excl_scan_u64((u64) a.totals[tid], &all_pairs);
+  u32 run = slot;
+#pragma unroll
+  for (u32 w = 0; w < kSortWaves; ++w) {
+    s_cnt[w][tid] = run;
+    run += c[w];
+  }
+  s_gbase[tid] = smaller + a.hist[(u64) tid * a.ntiles + blockIdx.x] - slot;
+  __syncthreads();
+#pragma unroll
+  for (u32 j = 0; j < kSortChunks; ++j) {
+    const u64 i = first + (u64) j * 64;
+    if (i < a.n) {
+      const u32 p = s_cnt[wave][sort_digit(key[j], a.kmin, a.shift)] + rank[j];
+      if (p < kSortTile) {
+        s_key[p] = key[j];
+        s_idx[p] = a.idx_in ? a.idx_in[i] : (u32) i;
+      }
+    }
+  }
+  __syncthreads();
+  for (u32 p = tid; p < tile_pairs && p < kSortTile; p += kBlock) {
+    const u64 k = s_key[p];
+    const u64 dst = s_gbase[sort_digit(k, a.kmin, a.shift)] + p;
+    if (dst < a.n) {
+      a.keys_out[dst] = k;
+      a.idx_out[dst] = s_idx[p];
+    }
+  }
+}
+
+// the permutation applied to a group of columns: perm is read once per group
+__global__ void __launch_bounds__(kBlock) k_cmp_permute(CmpPermuteArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    const u64 r = a.perm[i];
+    if (r >= a.n) {
+      a.status[0] = 1;
+      continue;
+    }
+    for (u32 c = 0; c < a.ncols; ++c) {
+      const CmpPermuteCol col = a.cols[c];
+      col.dst_vals[i] = col.src_vals[r];
+      if (col.dst_nulls) col.dst_nulls[i] = col.src_nulls[r];
+    }
+  }
+}
+
 // ---- nested scans over sibling repeated groups ---------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_record_starts(const u8* levels, const u64* tile_offsets,
                                                           u64 nslots, u64* starts, u64 max_starts) {
@@ -3698,6 +3886,37 @@ hipError_t launch_cmp_str_bytes(const CmpStrArgs& a, hipStream_t s) {
   const u64 ntiles = (a.n + kDecodeTile - 1) / kDecodeTile;
   if (ntiles == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cmp_str_bytes, dim3((unsigned) ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_key_stats(const uint64_t* keys, uint64_t n, uint64_t* stats, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sort_key_stats, dim3(grid_for(n, kBlock * 8, 2048)), dim3(kBlock), 0, s,
+                     (const u64*) keys, (u64) n, (u64*) stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_hist(const SortPassArgs& a, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sort_hist, dim3(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_digit_scan(const SortPassArgs& a, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sort_digit_scan, dim3(256), dim3(kBlock), 0, s, a.hist, a.ntiles, a.totals);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_scatter(const SortPassArgs& a, hipStream_t s) {
+  if (a.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sort_scatter, dim3(a.ntiles), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_permute(const CmpPermuteArgs& a, hipStream_t s) {
+  if (a.n == 0 || a.ncols == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cmp_permute, dim3(grid_for(a.n, kBlock, 8192)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -680,11 +680,13 @@ int evql_query_create_chain(evql_ctx_t* ctx, evql_lsm_chain_t* ch, const evql_pl
   API_CATCH
 }
 
-int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
-                           int row_order, int page_order, evql_table_t** out,
-                           evql_compact_stats_t* stats) {
+// evql_lsm_chain_compact and, with `sort`, evql_lsm_chain_compact_sorted
+static int compact_chain(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                         int row_order, int page_order, evql_table_t** out,
+                         evql_compact_stats_t* stats, const CompactSort* sort) {
   API_TRY
   if (!ch || !cols || !out || ncols <= 0) return fail(EVQL_EARG, "bad arguments");
+  if (sort && !sort->key_column) return fail(EVQL_EARG, "no key column");
   if (row_order != EVQL_COMPACT_SCAN_ORDER && row_order != EVQL_COMPACT_FILE_ORDER) {
     return fail(EVQL_EARG, "bad row order");
   }
@@ -698,11 +700,25 @@ int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols,
   }
   if (hipSetDevice(lsm_chain_ctx(ch)->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
   evql_table* t = nullptr;
-  Status st = chain_compact(ch, specs, row_order, page_order, &t, stats);
+  Status st = chain_compact(ch, specs, row_order, page_order, &t, stats, sort);
   if (!st.ok()) return ret(st);
   *out = t;
   return EVQL_OK;
   API_CATCH
+}
+
+int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                           int row_order, int page_order, evql_table_t** out,
+                           evql_compact_stats_t* stats) {
+  return compact_chain(ch, cols, ncols, row_order, page_order, out, stats, nullptr);
+}
+
+int evql_lsm_chain_compact_sorted(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                                  const char* key_column, int row_order, int page_order,
+                                  evql_table_t** out, evql_compact_stats_t* stats,
+                                  evql_compact_sort_stats_t* sort_stats) {
+  const CompactSort sort{key_column, sort_stats};
+  return compact_chain(ch, cols, ncols, row_order, page_order, out, stats, &sort);
 }
 
 void evql_query_destroy(evql_query_t* q) { delete q; }

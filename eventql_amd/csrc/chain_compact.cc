@@ -20,6 +20,20 @@
 //   6. encode    table_from_device_columns, as it is
 //   7. stats
 //
+// evql_lsm_chain_compact_sorted is the same call with three more steps; by 5b every flat
+// column is vals (+ nulls) over rows_out dense rows and a string's word is (len << 40) | heap
+// offset, so reordering the words reorders the strings without touching the heap:
+//
+//   3b. key statistics  min, max and descents of the gathered key words (k_sort_key_stats);
+//                       read back with step 4's wait, or with one of its own when no STRING
+//                       column is written
+//   5b. sort            no descent: nothing more.  Otherwise (key, u32 row) pairs through
+//                       ceil(bit_length(max - min) / 8) stable 8-bit passes over key - min
+//                       (k_sort_hist, k_sort_digit_scan, k_sort_scatter), ping-pong
+//   5c. permute         dst[i] = src[perm[i]] for the words and NULL bytes of the other
+//                       columns, in groups that share one read of perm (k_cmp_permute); the
+//                       key column takes the last pass's sorted words
+//
 // Output positions are fixed by the scans: no atomic decides where a row lands and no
 // workgroup waits for another.  Host waits of steps 2 - 5: one for the sizes that the host
 // must know (the flat total as a check against the chain's own counts, the slot totals of
@@ -53,6 +67,25 @@ struct OutColumn {
   DevBuf<uint64_t> d_str_tiles;
 };
 
+// columns that one k_cmp_permute launch moves: its destinations are staging beyond the table
+static const size_t kPermuteGroup = 4;
+
+// steps 3b, 5b, 5c of the sorted form
+struct SortJob {
+  size_t key = 0;                 // output column
+  bool own_wait = false;          // no STRING column: the statistics need a wait of their own
+  DevBuf<uint64_t> d_stats;       // [0..2] k_sort_key_stats, [3] k_cmp_permute's status
+  uint64_t* h_stats = nullptr;    // their four words of the pinned block
+  DevBuf<uint64_t> keys[2];       // the pairs, ping-pong
+  DevBuf<uint32_t> idx[2];
+  DevBuf<uint32_t> hist, totals;
+  std::vector<DevBuf<uint64_t>> free_vals;  // retired value / NULL buffers: the next
+  std::vector<DevBuf<uint8_t>> free_nulls;  // group's destinations
+  std::vector<CmpPermuteCol> h_cols;        // (lives until the stream has been synchronised)
+  DevBuf<CmpPermuteCol> d_cols;
+  evql_compact_sort_stats_t st{};
+};
+
 struct Job {
   evql_ctx* ctx = nullptr;
   hipStream_t s = nullptr;
@@ -67,6 +100,7 @@ struct Job {
   DevBuf<uint64_t> d_row_tiles;             // scanned kept rows per tile, all tables
   uint64_t* h_pinned = nullptr;             // the sizes the host reads back
   uint32_t launches = 0, waits = 0;
+  SortJob* sort = nullptr;                  // the sorted form
   const uint64_t* bits(size_t k) const { return reinterpret_cast<const uint64_t*>(d_filters[k]); }
 };
 
@@ -318,7 +352,7 @@ Status gather_strings(Job& j, uint64_t* string_bytes) {
   }
   *string_bytes = 0;
   if (str_cols.empty()) return Status();
-  if (str_cols.size() * 8 > kTailBlockBytes) return Status::error(EVQL_ENOTSUP, "too many string columns");
+  if ((str_cols.size() + 4) * 8 > kTailBlockBytes) return Status::error(EVQL_ENOTSUP, "too many string columns");
   auto str_args = [&](const OutColumn& oc, size_t si) {
     const Segment& sg = oc.segs[si];
     evql_table* t = j.tables[sg.table];
@@ -370,11 +404,143 @@ Status gather_strings(Job& j, uint64_t* string_bytes) {
   return Status();
 }
 
+// ---- 3b. key statistics ---------------------------------------------------------------------
+Status sort_key_stats(Job& j, hipEvent_t begin, hipEvent_t end) {
+  SortJob& sj = *j.sort;
+  const uint64_t n = j.plan.rows_out;
+  sj.own_wait = true;
+  for (const CompactColumn& pc : j.plan.columns) sj.own_wait = sj.own_wait && !pc.is_string;
+  sj.h_stats = j.h_pinned + kTailBlockBytes / 8 - 4;  // (the sizes of steps 2 and 4 lie in front)
+  HIP_TRY(sj.d_stats.alloc(4 * 8));
+  HIP_TRY(hipMemsetAsync(sj.d_stats, 0, 4 * 8, j.s));
+  HIP_TRY(hipEventRecord(begin, j.s));
+  if (n) {
+    HIP_TRY(launch_sort_key_stats(j.cols[sj.key].vals, n, sj.d_stats, j.s));
+    ++sj.st.n_kernel_launches;
+  }
+  HIP_TRY(hipEventRecord(end, j.s));
+  HIP_TRY(hipMemcpyAsync(sj.h_stats, sj.d_stats.p, 3 * 8, hipMemcpyDeviceToHost, j.s));
+  if (sj.own_wait) {
+    HIP_TRY(hipStreamSynchronize(j.s));
+    ++sj.st.n_host_waits;
+  }
+  return Status();
+}
+
+// ---- 5b. sort -------------------------------------------------------------------------------
+Status sort_rows(Job& j) {
+  SortJob& sj = *j.sort;
+  const uint64_t n = j.plan.rows_out;
+  sj.st.rows = n;
+  sj.st.key_min = n ? ~sj.h_stats[0] : 0;
+  sj.st.key_max = n ? sj.h_stats[1] : 0;
+  sj.st.presorted = sj.h_stats[2] == 0 || n <= 1;
+  if (sj.st.presorted) return Status();
+  uint32_t bits = 0;
+  for (uint64_t range = sj.st.key_max - sj.st.key_min; range; range >>= 1) ++bits;
+  sj.st.passes = (bits + 7) / 8;
+  SortPassArgs a{};
+  a.n = n;
+  a.kmin = sj.st.key_min;
+  a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
+  HIP_TRY(sj.hist.alloc(size_t(256) * a.ntiles * 4));
+  HIP_TRY(sj.totals.alloc(256 * 4));
+  a.hist = sj.hist;
+  a.totals = sj.totals;
+  for (uint32_t p = 0; p < sj.st.passes; ++p) {
+    const uint32_t to = p & 1, from = to ^ 1;
+    if (!sj.keys[to].p) {
+      HIP_TRY(sj.keys[to].alloc(n * 8));
+      HIP_TRY(sj.idx[to].alloc(n * 4));
+    }
+    // the first pass reads the gathered column; its rows are the identity
+    a.keys_in = p ? sj.keys[from].p : j.cols[sj.key].vals.p;
+    a.idx_in = p ? sj.idx[from].p : nullptr;
+    a.keys_out = sj.keys[to];
+    a.idx_out = sj.idx[to];
+    a.shift = 8 * p;
+    HIP_TRY(launch_sort_hist(a, j.s));
+    HIP_TRY(launch_sort_digit_scan(a, j.s));
+    HIP_TRY(launch_sort_scatter(a, j.s));
+    sj.st.n_kernel_launches += 3;
+  }
+  return Status();
+}
+
+// ---- 5c. permute ----------------------------------------------------------------------------
+Status permute_columns(Job& j) {
+  SortJob& sj = *j.sort;
+  const std::vector<ColumnSpec>& specs = *j.specs;
+  const uint64_t n = j.plan.rows_out;
+  const uint32_t last = (sj.st.passes - 1) & 1;
+  // the key column's sorted words are the last pass's; its gathered words and the other pair
+  // buffer are the first destinations
+  OutColumn& kc = j.cols[sj.key];
+  sj.free_vals.push_back(std::move(kc.vals));
+  kc.vals = std::move(sj.keys[last]);
+  if (sj.keys[last ^ 1].p) sj.free_vals.push_back(std::move(sj.keys[last ^ 1]));
+  std::vector<size_t> todo;
+  for (size_t c = 0; c < specs.size(); ++c) {
+    // (a constant column is the same in every order)
+    if (c != sj.key && !j.plan.columns[c].constant_false) todo.push_back(c);
+  }
+  if (todo.empty()) return Status();
+  sj.h_cols.resize(todo.size());
+  HIP_TRY(sj.d_cols.alloc(todo.size() * sizeof(CmpPermuteCol)));
+  std::vector<DevBuf<uint64_t>> dst_vals(todo.size());
+  std::vector<DevBuf<uint8_t>> dst_nulls(todo.size());
+  for (size_t g = 0; g < todo.size(); g += kPermuteGroup) {
+    const size_t ge = std::min(todo.size(), g + kPermuteGroup);
+    for (size_t x = g; x < ge; ++x) {
+      OutColumn& oc = j.cols[todo[x]];
+      if (!sj.free_vals.empty()) {
+        dst_vals[x] = std::move(sj.free_vals.back());
+        sj.free_vals.pop_back();
+      } else {
+        HIP_TRY(dst_vals[x].alloc(n * 8));
+      }
+      if (oc.nulls.p) {
+        if (!sj.free_nulls.empty()) {
+          dst_nulls[x] = std::move(sj.free_nulls.back());
+          sj.free_nulls.pop_back();
+        } else {
+          HIP_TRY(dst_nulls[x].alloc(n));
+        }
+      }
+      sj.h_cols[x] = CmpPermuteCol{oc.vals.p, dst_vals[x].p, oc.nulls.p, dst_nulls[x].p};
+    }
+    HIP_TRY(hipMemcpyAsync(sj.d_cols.p + g, sj.h_cols.data() + g, (ge - g) * sizeof(CmpPermuteCol),
+                           hipMemcpyHostToDevice, j.s));
+    CmpPermuteArgs a{};
+    a.perm = sj.idx[last];
+    a.n = n;
+    a.cols = sj.d_cols.p + g;
+    a.ncols = uint32_t(ge - g);
+    a.status = sj.d_stats.p + 3;
+    HIP_TRY(launch_cmp_permute(a, j.s));
+    ++sj.st.n_kernel_launches;
+    // the sources retire: the stream runs the next group behind this one
+    for (size_t x = g; x < ge; ++x) {
+      OutColumn& oc = j.cols[todo[x]];
+      sj.free_vals.push_back(std::move(oc.vals));
+      oc.vals = std::move(dst_vals[x]);
+      if (oc.nulls.p) {
+        sj.free_nulls.push_back(std::move(oc.nulls));
+        oc.nulls = std::move(dst_nulls[x]);
+      }
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(sj.h_stats + 3, sj.d_stats.p + 3, 8, hipMemcpyDeviceToHost, j.s));
+  return Status();
+}
+
 }  // namespace
 
 Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, int row_order,
-                     int page_order, evql_table** out, evql_compact_stats_t* stats) {
+                     int page_order, evql_table** out, evql_compact_stats_t* stats,
+                     const CompactSort* sort) {
   Job j;
+  SortJob sj;
   j.ctx = lsm_chain_ctx(ch);
   j.s = j.ctx->stream;
   j.specs = &specs;
@@ -383,8 +549,19 @@ Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, i
   const size_t nt = j.tables.size();
   for (size_t p = 0; p < nt; ++p) j.order.push_back(row_order == EVQL_COMPACT_FILE_ORDER ? nt - 1 - p : p);
 
+  if (sort) {
+    bool notsup = false;
+    const std::string err = plan_compact_sort_key(specs, sort->key_column, &sj.key, &notsup);
+    if (!err.empty()) return Status::error(notsup ? EVQL_ENOTSUP : EVQL_EARG, err);
+    j.sort = &sj;
+  }
   Status st = resolve_columns(j);
   if (!st.ok()) return st;
+  if (sort) {
+    bool notsup = false;
+    const std::string err = plan_compact_sort_rows(j.plan.rows_out, &notsup);
+    if (!err.empty()) return Status::error(EVQL_ENOTSUP, err);
+  }
 
   // the pinned block of the read-backs goes back to the pool on every path
   struct PinnedBlock {
@@ -398,14 +575,15 @@ Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, i
   HIP_TRY(pinned.pool->take(&pinned.p));
   j.h_pinned = static_cast<uint64_t*>(pinned.p);
   struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    // [0..2] gather, encode; the sorted form: [3..4] key statistics, [5] passes, [6] permutes
+    hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ~Events() {
       for (hipEvent_t x : e) {
         if (x) hipEventDestroy(x);
       }
     }
   } ev;
-  for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+  for (int i = 0; i < (sort ? 7 : 3); ++i) HIP_TRY(hipEventCreate(&ev.e[i]));
 
   HIP_TRY(hipEventRecord(ev.e[0], j.s));
   st = rank_kept(j);
@@ -413,11 +591,25 @@ Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, i
   DevBuf<CmpFixedCol> d_fixed_cols;
   std::vector<CmpFixedCol> h_fixed_cols;  // (lives until the stream has been synchronised)
   st = gather_fixed(j, &d_fixed_cols, &h_fixed_cols);
+  if (st.ok() && sort) st = sort_key_stats(j, ev.e[3], ev.e[4]);
   if (st.ok()) st = gather_slots(j);
   uint64_t string_bytes = 0;
   if (st.ok()) st = gather_strings(j, &string_bytes);
   if (!st.ok()) return st;
   HIP_TRY(hipEventRecord(ev.e[1], j.s));
+  hipEvent_t encode_begin = ev.e[1];
+  // ---- 5b. sort, 5c. permute (the sorted form only) -------------------------------------------
+  if (sort) {
+    st = sort_rows(j);
+    if (!st.ok()) return st;
+    if (!sj.st.presorted) {
+      HIP_TRY(hipEventRecord(ev.e[5], j.s));
+      st = permute_columns(j);
+      if (!st.ok()) return st;
+      HIP_TRY(hipEventRecord(ev.e[6], j.s));
+      encode_begin = ev.e[6];
+    }
+  }
 
   // ---- 6. encode ----------------------------------------------------------------------------
   std::vector<DeviceColumnIn> in;
@@ -432,6 +624,9 @@ Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, i
   std::unique_ptr<evql_table> owned(t);
   HIP_TRY(hipEventRecord(ev.e[2], j.s));
   HIP_TRY(hipEventSynchronize(ev.e[2]));
+  if (sort && !sj.st.presorted && sj.h_stats[3] != 0) {
+    return Status::error(EVQL_ERUNTIME, "the sort's permutation names a row behind the last");
+  }
 
   // ---- 7. stats -----------------------------------------------------------------------------
   if (stats) {
@@ -443,7 +638,19 @@ Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, i
     stats->n_kernel_launches = j.launches;
     stats->n_host_waits = j.waits;
     HIP_TRY(hipEventElapsedTime(&stats->gather_ms, ev.e[0], ev.e[1]));
-    HIP_TRY(hipEventElapsedTime(&stats->encode_ms, ev.e[1], ev.e[2]));
+    HIP_TRY(hipEventElapsedTime(&stats->encode_ms, encode_begin, ev.e[2]));
+  }
+  if (sort) {
+    // the key statistics ran inside the gather's span: their time is the sort's
+    float key_stats_ms = 0, passes_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&key_stats_ms, ev.e[3], ev.e[4]));
+    if (stats) stats->gather_ms = std::max(0.0f, stats->gather_ms - key_stats_ms);
+    if (!sj.st.presorted) {
+      HIP_TRY(hipEventElapsedTime(&passes_ms, ev.e[1], ev.e[5]));
+      HIP_TRY(hipEventElapsedTime(&sj.st.permute_ms, ev.e[5], ev.e[6]));
+    }
+    sj.st.sort_ms = key_stats_ms + passes_ms;
+    if (sort->stats) *sort->stats = sj.st;
   }
   *out = owned.release();
   return Status();

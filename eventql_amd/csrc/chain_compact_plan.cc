@@ -63,4 +63,43 @@ std::string plan_chain_compact(const std::vector<const TableLayout*>& tables,
   return std::string();
 }
 
+std::string plan_compact_sort_key(const std::vector<ColumnSpec>& specs, const char* key_column,
+                                  size_t* key_index, bool* not_supported) {
+  *not_supported = false;
+  *key_index = 0;
+  if (!key_column) return "no key column";
+  const std::string key(key_column);
+  size_t k = specs.size();
+  for (size_t i = 0; i < specs.size(); ++i) {
+    if (specs[i].name == key) k = i;
+  }
+  if (k == specs.size()) return "the key is not among the output columns: " + key;
+  const ColumnSpec& c = specs[k];
+  if (c.rlevel_max > 0 || c.dlevel_max > 1) return "the key is a repeated / nested column: " + key;
+  *not_supported = true;
+  if (c.dlevel_max > 0) return "sort key is an optional column (NULLs have no place in the order): " + key;
+  switch (c.logical_type) {
+    case ColumnType::UNSIGNED_INT:
+    case ColumnType::DATETIME: break;
+    case ColumnType::FLOAT: return "sort key is a float column: " + key;
+    case ColumnType::BOOLEAN: return "sort key is a boolean column: " + key;
+    case ColumnType::SIGNED_INT: return "sort key is a signed column: " + key;
+    case ColumnType::STRING: return "sort key is a string column: " + key;
+    default: return "sort key has no value words: " + key;
+  }
+  for (const ColumnSpec& o : specs) {
+    if (o.rlevel_max > 0 || o.dlevel_max > 1) {
+      return "sorted compaction of a repeated / nested column: " + o.name;
+    }
+  }
+  *not_supported = false;
+  *key_index = k;
+  return std::string();
+}
+
+std::string plan_compact_sort_rows(uint64_t rows_out, bool* not_supported) {
+  *not_supported = rows_out > 0xffffffffull;
+  return *not_supported ? "sorted compaction of more than 2^32 - 1 rows" : std::string();
+}
+
 }  // namespace evql

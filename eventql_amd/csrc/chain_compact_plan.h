@@ -38,4 +38,14 @@ std::string plan_chain_compact(const std::vector<const TableLayout*>& tables,
                                const std::vector<ColumnSpec>& specs, bool reverse_order,
                                CompactPlan* out);
 
+// The key rule of evql_lsm_chain_compact_sorted (include/evql_gpu.h): the key is one of
+// `specs`, flat and required, unsigned integer or datetime; no output column is repeated or
+// nested (the permutation moves rows, not records with their slot runs); the row index is u32.
+// Returns "" and *key_index, or the message of the error; *not_supported tells EVQL_ENOTSUP
+// from EVQL_EARG.  `key_column` may be NULL (EVQL_EARG).
+std::string plan_compact_sort_key(const std::vector<ColumnSpec>& specs, const char* key_column,
+                                  size_t* key_index, bool* not_supported);
+// rows_out of a plan that the sort can index
+std::string plan_compact_sort_rows(uint64_t rows_out, bool* not_supported);
+
 }  // namespace evql

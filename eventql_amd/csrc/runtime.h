@@ -655,8 +655,15 @@ evql_ctx* lsm_chain_ctx(const evql_lsm_chain* ch);
 // rows every table's filter keeps (all of them where it has none), in chain order
 void lsm_chain_rows_kept(const evql_lsm_chain* ch, std::vector<uint64_t>* kept);
 // chain_compact.cc: evql_lsm_chain_compact
+// `sort` != NULL: evql_lsm_chain_compact_sorted -- the same call with the key statistics, the
+// radix sort and the permutes between the gather and the writer
+struct CompactSort {
+  const char* key_column;
+  evql_compact_sort_stats_t* stats;  // may be NULL
+};
 Status chain_compact(evql_lsm_chain* ch, const std::vector<ColumnSpec>& specs, int row_order,
-                     int page_order, evql_table** out, evql_compact_stats_t* stats);
+                     int page_order, evql_table** out, evql_compact_stats_t* stats,
+                     const CompactSort* sort = nullptr);
 // the query's groups as dense records of rplan()'s layout: `dense` holds the first `nd`
 // groups, the remaining ngroups - nd sit in the HBM group table (compact them from there)
 struct RecordsView {

@@ -934,6 +934,53 @@ int evql_lsm_chain_compact(evql_lsm_chain_t* ch, const evql_column_spec_t* cols,
                            int row_order, int page_order,
                            evql_table_t** out, evql_compact_stats_t* stats /* may be NULL */);
 
+/*
+ * Sorted compaction: the rows evql_lsm_chain_compact writes, as ONE cstable, in ascending
+ * order of one key column -- the order that makes zone maps (evql_table_zone_map) narrow
+ * when the partition's files overlap in the key.  Rows, column rules (the keep rule, absent
+ * columns, __lsm_is_update, __lsm_skip) and `page_order` are exactly those of
+ * evql_lsm_chain_compact.
+ *
+ * Output order: the rows in the order evql_lsm_chain_compact(.., row_order, ..) writes them,
+ * sorted STABLY and ascending by the key column's 64-bit value word compared as unsigned:
+ * rows with equal keys keep the order of the plain compaction.  The sort is an LSD radix
+ * sort on the device between the gather and the writer: 8-bit digit passes over
+ * key - key_min, ceil(bit_length(key_max - key_min) / 8) of them; keys that are already
+ * non-descending (or rows <= 1) cost one read of the key words, run no pass and no permute,
+ * and the output is evql_lsm_chain_compact's byte for byte.
+ *
+ * `key_column` must be one of `cols`, flat and required (rlevel_max == 0, dlevel_max == 0),
+ * of logical type unsigned integer or datetime -- the columns that have zone maps.
+ *   EVQL_EARG    key_column is NULL, not among `cols`, or a repeated / nested column; null
+ *                arguments, ncols <= 0, a bad row_order or page_order, an unbuilt chain and
+ *                whatever evql_lsm_chain_compact answers EVQL_EARG to
+ *   EVQL_ENOTSUP (the message names the reason) an optional, float, boolean, signed or string
+ *                key; any output column with rlevel_max > 0 or dlevel_max > 1 (records would
+ *                have to move with their slot runs); more than 2^32 - 1 kept rows (the
+ *                permutation is u32)
+ *   EVQL_ERUNTIME a permutation entry behind the last row (nothing is stored for it)
+ *
+ * `stats` keeps its meaning: gather_ms does not include the sort or the permutes,
+ * n_kernel_launches and n_host_waits count the gather only, so the figures compare with the
+ * plain call's.  The sort's own figures go to `sort_stats`.
+ */
+typedef struct {
+  uint64_t rows;              /* rows sorted (= rows_written) */
+  uint64_t key_min, key_max;  /* over the kept rows; 0, 0 when rows == 0 */
+  uint32_t presorted;         /* 1: keys were already non-descending -> no pass, no permute */
+  uint32_t passes;            /* 8-bit digit passes actually run (0..8) */
+  uint32_t n_kernel_launches; /* of the sort and the permutes only */
+  uint32_t n_host_waits;      /* added by the sort (0 or 1): the key statistics ride on the
+                                 heap-size wait when a STRING column is written */
+  float sort_ms;              /* device time: key statistics + passes */
+  float permute_ms;           /* device time: applying the permutation to the columns */
+} evql_compact_sort_stats_t;
+
+int evql_lsm_chain_compact_sorted(evql_lsm_chain_t* ch, const evql_column_spec_t* cols, int ncols,
+                                  const char* key_column, int row_order, int page_order,
+                                  evql_table_t** out, evql_compact_stats_t* stats /* may be NULL */,
+                                  evql_compact_sort_stats_t* sort_stats /* may be NULL */);
+
 /* ------------------------------------------------------------------------ */
 /* build support                                                              */
 /* ------------------------------------------------------------------------ */
