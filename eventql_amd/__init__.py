@@ -142,6 +142,7 @@ def lib():
     L.evql_lsm_chain_filter.argtypes = [C.c_void_p, C.c_int, C.POINTER(_u8p), _u64p, _u64p]
     K.bind_chain_compact(L)
     K.bind_chain_compact_sorted(L)
+    K.bind_partial_emit(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_destroy.argtypes = [C.c_void_p]
     L.evql_merge_add_frame.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -279,6 +280,19 @@ class Context:
         st = K.KernelCacheStats()
         _check(lib().evql_ctx_kernel_cache_stats(self.h, C.byref(st)))
         return st
+
+    def sha1_ranges(self, chunks):
+        """evql_ctx_sha1_ranges: the SHA-1 digests (20 bytes each) of a list of byte strings,
+        computed by the kernel that hashes the group tuples of PARTIAL rows"""
+        chunks = [bytes(c) for c in chunks]
+        n = len(chunks)
+        offs = (C.c_uint64 * (n + 1))()
+        for i, c in enumerate(chunks):
+            offs[i + 1] = offs[i] + len(c)
+        blob = b"".join(chunks)
+        out = C.create_string_buffer(max(1, 20 * n))
+        _check(lib().evql_ctx_sha1_ranges(self.h, blob, len(blob), offs, n, out))
+        return [out.raw[20 * i:20 * i + 20] for i in range(n)]
 
     def open_file(self, path):
         t = C.c_void_p()
@@ -483,6 +497,12 @@ class Query:
         _check(lib().evql_query_zone_stats(self.h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in K.ZoneStats._fields_}
 
+    def emit_stats(self):
+        """evql_query_emit_stats: how the last fetched result left the device"""
+        s = K.EmitStats()
+        _check(lib().evql_query_emit_stats(self.h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in K.EmitStats._fields_}
+
     def kernel_source(self):
         return lib().evql_query_kernel_source(self.h).decode()
 
@@ -661,12 +681,7 @@ class Merge:
         self.close()
 
 
-def compile_only(plan, columns, cache_dir=None):
-    """compile the fused kernel of `plan` for gfx950 without a device.
-    columns: list of dict(name, logical_type, storage_type, dlevel_max=0, bits=0,
-    narrow_bits=0); bits = width of a bit-packed file column, narrow_bits = 8 / 16 / 32: a
-    required UINT64_PLAIN / LEB128 column as read from the flat narrow copy a table keeps;
-    narrow_bits = 32 on a required FLOAT_IEEE754 column: as read from its float32 copy"""
+def _column_infos(columns):
     infos = (K.ColumnInfo * len(columns))()
     for i, c in enumerate(columns):
         infos[i].name = c["name"].encode()
@@ -676,6 +691,27 @@ def compile_only(plan, columns, cache_dir=None):
         infos[i].dlevel_max = c.get("dlevel_max", 0)
         infos[i].rlevel_max = c.get("rlevel_max", 0)
         infos[i].payload_bytes = c.get("narrow_bits", 0) or c.get("bits", 0)
+    return infos
+
+
+def plan_partial_emit(plan, columns, n_groups, merged=False):
+    """evql_plan_partial_emit: would a result of n_groups groups of `plan` leave as
+    device-packed PARTIAL rows?  capi.PEMIT_DEVICE (0) or the reason why not; no device
+    needed, columns as for compile_only"""
+    infos = _column_infos(columns)
+    d = C.c_int()
+    _check(lib().evql_plan_partial_emit(C.byref(plan.desc), infos, len(columns), n_groups,
+                                        int(merged), C.byref(d)))
+    return d.value
+
+
+def compile_only(plan, columns, cache_dir=None):
+    """compile the fused kernel of `plan` for gfx950 without a device.
+    columns: list of dict(name, logical_type, storage_type, dlevel_max=0, bits=0,
+    narrow_bits=0); bits = width of a bit-packed file column, narrow_bits = 8 / 16 / 32: a
+    required UINT64_PLAIN / LEB128 column as read from the flat narrow copy a table keeps;
+    narrow_bits = 32 on a required FLOAT_IEEE754 column: as read from its float32 copy"""
+    infos = _column_infos(columns)
     size = C.c_size_t()
     cd = (cache_dir or KERNEL_CACHE_DIR).encode()
     _check(lib().evql_compile_only(C.byref(plan.desc), infos, len(columns), cd, C.byref(size)))

@@ -177,6 +177,35 @@ class ZoneStats(C.Structure):
     ]
 
 
+class EmitStats(C.Structure):
+    """evql_emit_stats_t"""
+    _fields_ = [
+        ("device_packed", C.c_uint32),
+        ("partial", C.c_uint32),
+        ("rows", C.c_uint64),
+        ("key_bytes", C.c_uint64),
+        ("data_bytes", C.c_uint64),
+        ("n_kernel_launches", C.c_uint32),
+        ("n_host_waits", C.c_uint32),
+        ("pack_ms", C.c_double),
+    ]
+
+
+# *decision of evql_plan_partial_emit
+PEMIT_DEVICE, PEMIT_NOT_PARTIAL, PEMIT_FEW_GROUPS, PEMIT_SWITCHED_OFF, PEMIT_GROUP_EXPR = range(5)
+PEMIT_SELECT_EXPR, PEMIT_AGGREGATE, PEMIT_TOO_WIDE, PEMIT_NIL_COLUMN, PEMIT_NESTED = range(5, 10)
+DEVICE_EMIT_MIN_GROUPS = 1 << 16
+
+
+def bind_partial_emit(lib):
+    """declares evql_query_emit_stats, evql_ctx_sha1_ranges and evql_plan_partial_emit"""
+    lib.evql_query_emit_stats.argtypes = [C.c_void_p, C.POINTER(EmitStats)]
+    lib.evql_ctx_sha1_ranges.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t,
+                                         C.POINTER(C.c_uint64), C.c_size_t, C.c_char_p]
+    lib.evql_plan_partial_emit.argtypes = [C.POINTER(PlanDesc), C.POINTER(ColumnInfo), C.c_int,
+                                           C.c_uint64, C.c_int, C.POINTER(C.c_int)]
+
+
 class KernelCacheStats(C.Structure):
     _fields_ = [
         ("memory_hits", C.c_uint64),

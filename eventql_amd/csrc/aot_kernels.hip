@@ -2340,6 +2340,221 @@ __global__ void __launch_bounds__(kBlock) k_emit_str_bytes(const EmitArgs* ap, u
   }
 }
 
+// ---- EVQL_MODE_PARTIAL rows on the device (results.cc emit_partial_on_device) ----------
+// One thread per group everywhere; sizes and bytes come from the same two helpers, so every
+// store lies inside the group's scanned range.
+__device__ __forceinline__ u32 varuint_len(u64 v) {
+  return v == 0 ? 1u : (u32) ((64 - __clzll((long long) v) + 6) / 7);
+}
+__device__ __forceinline__ u32 put_varuint(u8* p, u64 v) {
+  u32 k = 0;
+  do {
+    u8 x = (u8) (v & 0x7f);
+    v >>= 7;
+    if (v) x |= 0x80;
+    p[k++] = x;
+  } while (v);
+  return k;
+}
+
+// bytes of the SVector element of a key / first-row cell of group i
+__device__ __forceinline__ u32 pcell_size(const PartialArgs& a, const PartialCell& c, u64 i) {
+  if (c.is_bool) return 2;
+  if (!c.is_string) return 9;
+  const bool null = a.first_tags[(u64) c.src * a.n + i] & 1;
+  const u64 sp = ((const u64*) a.first_vals)[(u64) c.src * a.n + i];
+  return 5 + (null ? 0u : (u32) (sp >> 40));
+}
+
+// ... and the element itself.  boxed: the cell leaves through SValue::encode, where a value of
+// exactly 16 bytes -- a string of 11 -- keeps STAG_INLINE (bit 7) in its tag (svalue.cc:346-368)
+__device__ __forceinline__ u32 pcell_write(const PartialArgs& a, const PartialCell& c, const u64* rec,
+                                           u64 i, u8* p, bool boxed) {
+  u64 bits = 0;
+  u8 tag = 0;
+  if (c.kind == 0) {
+    if (rec[0] == 2) tag = kStagNull; else bits = rec[1];
+  } else {
+    const u64 raw = ((const u64*) a.first_vals)[(u64) c.src * a.n + i];
+    tag = a.first_tags[(u64) c.src * a.n + i] & 1 ? kStagNull : 0;
+    if (c.is_string) {
+      const u32 len = tag ? 0u : (u32) (raw >> 40);
+      const u64 off = raw & kStrOffMask;
+      p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
+      for (u32 k = 0; k < len; ++k) p[4 + k] = vbyte_fwd(a.image, (const u64*) c.pages, off + k);
+      if (boxed && len == 11) tag |= 0x80;
+      p[4 + len] = tag;
+      return 5 + len;
+    }
+    bits = c.to_float ? evql_f64_bits((double) raw) : raw;
+  }
+  if (c.is_bool) {
+    p[0] = (u8) (bits != 0);
+    p[1] = tag;
+    return 2;
+  }
+#pragma unroll
+  for (int b = 0; b < 8; ++b) p[b] = (u8) (bits >> (8 * b));
+  p[8] = tag;
+  return 9;
+}
+
+__global__ void __launch_bounds__(kBlock) k_partial_sizes(const PartialArgs* ap, u64 n, u64* tuple_size,
+                                                          u64* data_size) {
+  const PartialArgs& a = *ap;
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64* rec = (const u64*) a.records + i * a.rw;
+    u64 ts = 0;
+    for (u32 c = 0; c < a.n_tuple; ++c) ts += pcell_size(a, a.tuple[c], i);
+    u64 ds = 5;  // u32 length in front, the tag behind
+    for (u32 c = 0; c < a.n_data; ++c) {
+      const PartialCell& e = a.data[c];
+      if (e.kind == 1) {
+        // instance_savestate: count / integer sum = varuint; sum(float64) = 8 bytes;
+        // min / max / mean = varuint(count) + 8 bytes
+        if (e.state == PSTATE_VARUINT) ds += varuint_len(rec[e.word]);
+        else if (e.state == PSTATE_RAW8) ds += 8;
+        else ds += varuint_len(rec[e.word + 1]) + 8;
+      } else {
+        // SValue::encode: u8 type, varuint(element bytes), the element
+        const u32 el = pcell_size(a, e, i);
+        ds += 1 + varuint_len(el) + el;
+      }
+    }
+    tuple_size[i] = ts;
+    data_size[i] = ds;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_partial_tuple_bytes(const PartialArgs* ap, u64 n,
+                                                                const u64* tuple_off, u8* heap) {
+  const PartialArgs& a = *ap;
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64* rec = (const u64*) a.records + i * a.rw;
+    u8* p = heap + tuple_off[i];
+    for (u32 c = 0; c < a.n_tuple; ++c) p += pcell_write(a, a.tuple[c], rec, i, p, false);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_partial_data_bytes(const PartialArgs* ap, u64 n,
+                                                               const u64* data_off, u8* out) {
+  const PartialArgs& a = *ap;
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64* rec = (const u64*) a.records + i * a.rw;
+    u8* p = out + data_off[i];
+    const u32 len = (u32) (data_off[i + 1] - data_off[i] - 5);  // (data_off[n] = the total)
+    p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
+    p[4 + len] = 0;
+    p += 4;
+    for (u32 c = 0; c < a.n_data; ++c) {
+      const PartialCell& e = a.data[c];
+      if (e.kind == 1) {
+        const u64 w0 = rec[e.word];
+        if (e.state == PSTATE_VARUINT) {
+          p += put_varuint(p, w0);
+          continue;
+        }
+        u64 bits = w0;
+        if (e.state == PSTATE_COUNT_RAW8) {
+          // a group without a non-NULL value: the word still holds the operation's identity,
+          // on the wire an untouched state is 0
+          const u64 cnt = rec[e.word + 1];
+          p += put_varuint(p, cnt);
+          if (cnt == 0) bits = 0;
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) p[b] = (u8) (bits >> (8 * b));
+        p += 8;
+      } else {
+        p[0] = (u8) e.stype;
+        p += 1 + put_varuint(p + 1, pcell_size(a, e, i));
+        p += pcell_write(a, e, rec, i, p, true);
+      }
+    }
+  }
+}
+
+// FIPS 180-4 SHA-1, one thread per byte range.  Big-endian word k / 4 of the padded message:
+// the message bytes, 0x80, zeros (the bit length goes into the last block's words 14 / 15).
+__device__ __forceinline__ u32 sha1_word(const u8* m, u64 len, u64 k) {
+  if (k + 4 <= len) {
+    u32 w;
+    __builtin_memcpy(&w, m + k, 4);
+    return __builtin_bswap32(w);
+  }
+  u32 w = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const u64 b = k + j;
+    const u32 v = b < len ? (u32) m[b] : (b == len ? 0x80u : 0u);
+    w = (w << 8) | v;
+  }
+  return w;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sha1_ranges(const u8* heap, const u64* offsets, u64 n,
+                                                        u8* out, u32 out_stride, u32 out_prefix) {
+  for (u64 g = (u64) blockIdx.x * blockDim.x + threadIdx.x; g < n;
+       g += (u64) gridDim.x * blockDim.x) {
+    const u64 b0 = offsets[g], b1 = offsets[g + 1];
+    const u64 len = b1 > b0 ? b1 - b0 : 0;
+    const u8* m = heap + b0;
+    u32 h0 = 0x67452301u, h1 = 0xEFCDAB89u, h2 = 0x98BADCFEu, h3 = 0x10325476u, h4 = 0xC3D2E1F0u;
+    const u64 nblocks = (len + 8) / 64 + 1;  // 0x80 and the 8 length bytes fit behind the message
+    for (u64 blk = 0; blk < nblocks; ++blk) {
+      // the message schedule as a ring of 16 words; all 80 rounds unrolled, so that every
+      // index is a constant and the ring stays in registers
+      u32 w[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) w[j] = sha1_word(m, len, blk * 64 + 4 * j);
+      if (blk + 1 == nblocks) {
+        w[14] = (u32) ((len * 8) >> 32);
+        w[15] = (u32) (len * 8);
+      }
+      u32 a = h0, b = h1, c = h2, d = h3, e = h4;
+#pragma unroll
+      for (int t = 0; t < 80; ++t) {
+        u32 wt;
+        if (t < 16) {
+          wt = w[t];
+        } else {
+          wt = __builtin_rotateleft32(w[(t + 13) & 15] ^ w[(t + 8) & 15] ^ w[(t + 2) & 15] ^ w[t & 15], 1);
+          w[t & 15] = wt;
+        }
+        u32 f, k;
+        if (t < 20) { f = (b & c) | (~b & d); k = 0x5A827999u; }
+        else if (t < 40) { f = b ^ c ^ d; k = 0x6ED9EBA1u; }
+        else if (t < 60) { f = (b & c) | (b & d) | (c & d); k = 0x8F1BBCDCu; }
+        else { f = b ^ c ^ d; k = 0xCA62C1D6u; }
+        const u32 tmp = __builtin_rotateleft32(a, 5) + f + e + k + wt;
+        e = d;
+        d = c;
+        c = __builtin_rotateleft32(b, 30);
+        b = a;
+        a = tmp;
+      }
+      h0 += a; h1 += b; h2 += c; h3 += d; h4 += e;
+    }
+    u8* o = out + g * out_stride;
+    if (out_prefix) {  // the digest as a STRING element: u32 20, the bytes, tag 0
+      o[0] = 20; o[1] = 0; o[2] = 0; o[3] = 0;
+      o[24] = 0;
+      o += 4;
+    }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      o[b] = (u8) (h0 >> (24 - 8 * b));
+      o[4 + b] = (u8) (h1 >> (24 - 8 * b));
+      o[8 + b] = (u8) (h2 >> (24 - 8 * b));
+      o[12 + b] = (u8) (h3 >> (24 - 8 * b));
+      o[16 + b] = (u8) (h4 >> (24 - 8 * b));
+    }
+  }
+}
+
 // ---- string dictionaries (string_dict.cc) ---------------------------------------------
 // records of the dictionary's GROUP BY over the column's 64-bit string hash:
 // [kind, hash, first row, count]; record i becomes code i
@@ -3250,6 +3465,38 @@ hipError_t launch_emit_str_sizes(const EmitArgs* d_args, uint32_t c, uint64_t n,
 hipError_t launch_emit_str_bytes(const EmitArgs* d_args, uint32_t c, uint64_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_emit_str_bytes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, c, (u64) n);
+  return hipGetLastError();
+}
+
+hipError_t launch_partial_sizes(const PartialArgs* d_args, uint64_t n, uint64_t* tuple_size,
+                                uint64_t* data_size, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_partial_sizes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, (u64) n,
+                     (u64*) tuple_size, (u64*) data_size);
+  return hipGetLastError();
+}
+
+hipError_t launch_partial_tuple_bytes(const PartialArgs* d_args, uint64_t n, const uint64_t* tuple_off,
+                                      uint8_t* heap, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_partial_tuple_bytes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, (u64) n,
+                     (const u64*) tuple_off, heap);
+  return hipGetLastError();
+}
+
+hipError_t launch_partial_data_bytes(const PartialArgs* d_args, uint64_t n, const uint64_t* data_off,
+                                     uint8_t* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_partial_data_bytes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, (u64) n,
+                     (const u64*) data_off, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sha1_ranges(const uint8_t* heap, const uint64_t* offsets, uint64_t n, uint8_t* out,
+                              uint32_t out_stride, uint32_t out_prefix, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sha1_ranges, dim3(grid_for(n)), dim3(kBlock), 0, s, heap, (const u64*) offsets,
+                     (u64) n, out, out_stride, out_prefix);
   return hipGetLastError();
 }
 

@@ -598,6 +598,10 @@ static int create_one(evql_ctx_t* ctx, evql_table_t* table, const evql_plan_desc
     if (strcmp(et, "0") == 0) q->eager_tail = evql_query::EAGER_OFF;
     if (strcmp(et, "records") == 0) q->eager_tail = evql_query::EAGER_RECORDS;
   }
+  // EVQL_PARTIAL_DEVICE_EMIT=0: PARTIAL rows of large results keep the host loop
+  if (const char* pe = getenv("EVQL_PARTIAL_DEVICE_EMIT")) {
+    if (strcmp(pe, "0") == 0) q->partial_device_emit = false;
+  }
   if (plan->group_mode != EVQL_MODE_FINAL && plan->group_mode != EVQL_MODE_PARTIAL) {
     return fail(EVQL_EARG, "bad group mode");
   }
@@ -867,6 +871,15 @@ int evql_query_zone_stats(const evql_query_t* q, evql_zone_stats_t* out) {
   return EVQL_OK;
 }
 
+int evql_query_emit_stats(const evql_query_t* q, evql_emit_stats_t* out) {
+  if (!q || !out) return fail(EVQL_EARG, "null argument");
+  if (q->kp.bare_scan || !q->executed || !q->fetched) {
+    return fail(EVQL_EARG, "no result was fetched");
+  }
+  *out = q->estats;
+  return EVQL_OK;
+}
+
 const char* evql_query_kernel_source(const evql_query_t* q) { return q->source.c_str(); }
 
 // ---- partial aggregates ---------------------------------------------------------------
@@ -1084,6 +1097,53 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
   st = compile_to_code_object(q.source, &code, true);
   if (!st.ok()) return ret(st);
   if (code_size) *code_size = code.size();
+  return EVQL_OK;
+  API_CATCH
+}
+
+int evql_ctx_sha1_ranges(evql_ctx_t* ctx, const void* bytes, size_t len, const uint64_t* offsets,
+                         size_t n, uint8_t* out20) {
+  API_TRY
+  if (!ctx || !offsets || (!bytes && len) || (!out20 && n)) return fail(EVQL_EARG, "null argument");
+  for (size_t i = 0; i <= n; ++i) {
+    if (offsets[i] > len) return fail(EVQL_EARG, "offset beyond the bytes");
+    if (i && offsets[i] < offsets[i - 1]) return fail(EVQL_EARG, "offsets decrease");
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  return ret(sha1_ranges_on_device(ctx, bytes, len, offsets, n, out20));
+  API_CATCH
+}
+
+int evql_plan_partial_emit(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                           int ncolumns, uint64_t n_groups, int merged, int* decision) {
+  API_TRY
+  if (!plan || (!columns && ncolumns) || !decision) return fail(EVQL_EARG, "null argument");
+  TableLayout layout;
+  layout.version = 2;
+  layout.num_rows = 0;
+  for (int i = 0; i < ncolumns; ++i) {
+    ColumnLayout c;
+    c.name = columns[i].name;
+    c.logical_type = ColumnType(columns[i].logical_type);
+    c.storage_type = ColumnEncoding(columns[i].storage_type);
+    c.column_id = columns[i].column_id;
+    c.rlevel_max = columns[i].rlevel_max;
+    c.dlevel_max = columns[i].dlevel_max;
+    layout.columns.push_back(c);
+  }
+  evql_query q;
+  q.group_mode = plan->group_mode;
+  q.float_sum_mode = plan->float_sum_mode;
+  q.float_sum_bound = plan->float_sum_bound;
+  bool unsupported = false;
+  Status st = build_kernel_plan(layout, plan, &q, &unsupported);
+  if (!st.ok()) return ret(st);
+  if (const char* pe = getenv("EVQL_PARTIAL_DEVICE_EMIT")) {
+    if (strcmp(pe, "0") == 0) q.partial_device_emit = false;
+  }
+  q.merged = merged != 0;
+  PartialEmitPlan pplan;
+  *decision = int(plan_partial_emit(partial_emit_input(&q, n_groups), &pplan));
   return EVQL_OK;
   API_CATCH
 }

@@ -19,8 +19,34 @@ namespace evql {
 // kernel writes the packed SVector bytes (svalue.cc:410-517) of every column for ALL groups;
 // the host copies each column once into pinned memory and next_batch hands out slices.
 // Row order is unspecified for a GROUP BY; small results keep the host path
-// and its deterministic order.
-static const uint64_t kDeviceEmitMinGroups = 1 << 16;
+// and its deterministic order.  (kDeviceEmitMinGroups: partial_emit_plan.h)
+
+// device time and work of one packing: evql_query_emit_stats
+struct PackMeter {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  uint32_t launches = 0, waits = 0;
+  ~PackMeter() {
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+  }
+  hipError_t begin(hipStream_t s) {
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, s);
+    return e;
+  }
+  // in front of the last synchronisation of the packing ...
+  hipError_t mark_end(hipStream_t s) { return hipEventRecord(e1, s); }
+  // ... and behind it
+  hipError_t finish(evql_emit_stats_t* st) {
+    float ms = 0;
+    hipError_t e = hipEventElapsedTime(&ms, e0, e1);
+    st->pack_ms = ms;
+    st->n_kernel_launches = launches;
+    st->n_host_waits = waits;
+    return e;
+  }
+};
 
 static bool device_emit_columns(const evql_query* q, bool merged, EmitArgs* ea) {
   const KernelPlan& kp = q->rplan();
@@ -92,6 +118,8 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
   hipStream_t s = q->ctx->stream;
   const uint32_t nsel = ea.ncols;
   evql_query::DeviceEmit& de = q->demit;
+  PackMeter pm;
+  HIP_TRY(pm.begin(s));
   de.col.resize(nsel, nullptr);
   de.col_cap.resize(nsel, 0);
   de.off.resize(nsel, nullptr);
@@ -120,6 +148,8 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
     HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
     HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
     HIP_TRY(hipStreamSynchronize(s));  // (rc lives until here)
+    pm.launches += 2;
+    ++pm.waits;
     ea.first_vals = d_vals;
     ea.first_tags = d_tags;
   }
@@ -142,6 +172,7 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
   }
   HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
   HIP_TRY(launch_emit_fixed(d_args, n, s));
+  ++pm.launches;
   bool strings = false;
   for (uint32_t i = 0; i < nsel; ++i) {
     if (ea.col[i].elem) continue;
@@ -149,8 +180,10 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
     HIP_TRY(launch_emit_str_sizes(d_args, i, n, d_off[i], s));
     HIP_TRY(launch_exclusive_scan(d_off[i], n, d_off[i].p + n, s));
     HIP_TRY(hipMemcpyAsync(&str_bytes[i], d_off[i].p + n, 8, hipMemcpyDeviceToHost, s));
+    pm.launches += 2;
   }
   HIP_TRY(hipStreamSynchronize(s));
+  ++pm.waits;
   if (strings) {
     for (uint32_t i = 0; i < nsel; ++i) {
       if (ea.col[i].elem) continue;
@@ -160,7 +193,9 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
     }
     HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
     for (uint32_t i = 0; i < nsel; ++i) {
-      if (!ea.col[i].elem) HIP_TRY(launch_emit_str_bytes(d_args, i, n, s));
+      if (ea.col[i].elem) continue;
+      HIP_TRY(launch_emit_str_bytes(d_args, i, n, s));
+      ++pm.launches;
     }
   }
   // one copy per column into pinned host memory
@@ -177,8 +212,149 @@ static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec,
       HIP_TRY(hipMemcpyAsync(de.off[i], d_off[i], (n + 1) * 8, hipMemcpyDeviceToHost, s));
     }
   }
+  HIP_TRY(pm.mark_end(s));
   HIP_TRY(hipStreamSynchronize(s));
+  ++pm.waits;
+  HIP_TRY(pm.finish(&q->estats));
   de.active = true;
+  return Status();
+}
+
+// ---------------------------------------------------------------------------
+// large EVQL_MODE_PARTIAL results: the (key, data) rows packed on the device
+// ---------------------------------------------------------------------------
+// PartialGroupByExpression (groupby.cc:438-472) sends (SHA-1 of the group tuple, concatenated
+// saved states) per group.  The row loop of query_next_batch boxes every cell, allocates three
+// vectors and runs one host sha1() per group.  For the plans plan_partial_emit accepts the same
+// bytes are written by kernels: per-group sizes, two scans, the tuple heap (staging: only its
+// digests leave the device), the data column, SHA-1 per tuple.
+PartialEmitInput partial_emit_input(const evql_query* q, uint64_t n) {
+  PartialEmitInput in;
+  in.group_mode = q->group_mode;
+  in.n = n;
+  in.enabled = q->partial_device_emit;
+  in.merged = q->merged;
+  in.nested = q->nested;
+  in.kp = &q->rplan();
+  in.scan_select = &q->scan_select;
+  in.group = &q->group;
+  in.select = &q->select;
+  in.select_agg_index = &q->select_agg_index;
+  in.select_passthrough = &q->select_passthrough;
+  return in;
+}
+
+static Status emit_partial_on_device(evql_query* q, const PartialEmitPlan& plan, const uint64_t* d_rec,
+                                     uint64_t n, uint32_t nwords) {
+  evql_table* t = q->table;
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = q->ctx->stream;
+  evql_query::DeviceEmit& de = q->demit;
+  PackMeter pm;
+  HIP_TRY(pm.begin(s));
+  de.col.resize(2, nullptr);
+  de.col_cap.resize(2, 0);
+  de.off.resize(2, nullptr);
+  de.off_cap.resize(2, 0);
+  de.elem.assign(2, 0);
+  de.elem[0] = 25;  // u32 20, the digest, tag 0
+  PartialArgs pa{};
+  pa.records = d_rec;
+  pa.n = n;
+  pa.rw = nwords + 1;
+  pa.image = t->d_image;
+  pa.n_tuple = uint32_t(plan.tuple.size());
+  pa.n_data = uint32_t(plan.data.size());
+  for (uint32_t i = 0; i < pa.n_tuple; ++i) {
+    pa.tuple[i] = plan.tuple[i];
+    if (pa.tuple[i].is_string) pa.tuple[i].pages = t->d_pages[kp.cols[pa.tuple[i].src].layout_index][0];
+  }
+  for (uint32_t i = 0; i < pa.n_data; ++i) {
+    pa.data[i] = plan.data[i];
+    if (pa.data[i].is_string) pa.data[i].pages = t->d_pages[kp.cols[pa.data[i].src].layout_index][0];
+  }
+  DevBuf<uint64_t> d_rows, d_vals;
+  DevBuf<uint8_t> d_tags;
+  DevBuf<RtColumn> d_cols;
+  std::vector<RtColumn> rc;  // (lives until the first synchronisation below)
+  const uint32_t nc = uint32_t(kp.cols.size());
+  if (plan.need_first) {
+    // the column values of every group's first row (strings: their strpos words)
+    Status stc = first_row_columns(q, &rc);
+    if (!stc.ok()) return stc;
+    HIP_TRY(d_rows.alloc(n * 8));
+    HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
+    HIP_TRY(d_vals.alloc(n * nc * 8));
+    HIP_TRY(d_tags.alloc(n * nc));
+    HIP_TRY(launch_extract_word(d_rec, n, nwords + 1, uint32_t(1 + kp.first_row_word()), d_rows, s));
+    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
+    pm.launches += 2;
+    pa.first_vals = d_vals;
+    pa.first_tags = d_tags;
+  }
+  // sizes -> offsets; one wait reads both totals
+  DevBuf<PartialArgs> d_args;
+  DevBuf<uint64_t> d_toff, d_doff;
+  HIP_TRY(d_args.alloc(sizeof(PartialArgs)));
+  HIP_TRY(d_toff.alloc((n + 2) * 8));
+  HIP_TRY(d_doff.alloc((n + 2) * 8));
+  HIP_TRY(hipMemcpyAsync(d_args, &pa, sizeof(PartialArgs), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_partial_sizes(d_args, n, d_toff, d_doff, s));
+  HIP_TRY(launch_exclusive_scan(d_toff, n, d_toff.p + n, s));
+  HIP_TRY(launch_exclusive_scan(d_doff, n, d_doff.p + n, s));
+  uint64_t totals[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&totals[0], d_toff.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&totals[1], d_doff.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  pm.launches += 3;
+  ++pm.waits;
+  // bytes and digests
+  DevBuf<uint8_t> d_theap, d_data, d_key;
+  HIP_TRY(d_theap.alloc(totals[0] + 16));
+  HIP_TRY(d_data.alloc(totals[1] + 16));
+  HIP_TRY(d_key.alloc(n * 25));
+  HIP_TRY(launch_partial_tuple_bytes(d_args, n, d_toff, d_theap, s));
+  HIP_TRY(launch_partial_data_bytes(d_args, n, d_doff, d_data, s));
+  HIP_TRY(launch_sha1_ranges(d_theap, d_toff, n, d_key, 25, 1, s));
+  pm.launches += 3;
+  // one copy per column into pinned host memory
+  Status st = pinned_reserve(&de.col[0], &de.col_cap[0], n * 25);
+  if (!st.ok()) return st;
+  st = pinned_reserve(&de.col[1], &de.col_cap[1], totals[1]);
+  if (!st.ok()) return st;
+  uint8_t* po = reinterpret_cast<uint8_t*>(de.off[1]);
+  st = pinned_reserve(&po, &de.off_cap[1], (n + 1) * 8);
+  de.off[1] = reinterpret_cast<uint64_t*>(po);
+  if (!st.ok()) return st;
+  HIP_TRY(hipMemcpyAsync(de.col[0], d_key, n * 25, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(de.col[1], d_data, totals[1], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(de.off[1], d_doff, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(pm.mark_end(s));
+  HIP_TRY(hipStreamSynchronize(s));
+  ++pm.waits;
+  HIP_TRY(pm.finish(&q->estats));
+  q->estats.key_bytes = n * 25;
+  q->estats.data_bytes = totals[1];
+  de.active = true;
+  return Status();
+}
+
+// evql_ctx_sha1_ranges: k_sha1_ranges over host bytes (offsets validated by the caller)
+Status sha1_ranges_on_device(evql_ctx* ctx, const void* bytes, size_t len, const uint64_t* offsets,
+                             size_t n, uint8_t* out20) {
+  if (n == 0) return Status();
+  hipStream_t s = ctx->stream;
+  DevBuf<uint8_t> d_bytes, d_out;
+  DevBuf<uint64_t> d_off;
+  HIP_TRY(d_bytes.alloc(len));
+  HIP_TRY(d_off.alloc((n + 1) * 8));
+  HIP_TRY(d_out.alloc(n * 20));
+  if (len) HIP_TRY(hipMemcpyAsync(d_bytes, bytes, len, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_sha1_ranges(d_bytes, d_off, n, d_out, 20, 0, s));
+  HIP_TRY(hipMemcpyAsync(out20, d_out, n * 20, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return Status();
 }
 
@@ -508,7 +684,11 @@ static Status fetch_results(evql_query* q) {
   q->ngroups = n;
   q->rec_stride = r.nwords + 1;
   q->demit.active = false;
+  q->estats = evql_emit_stats_t{};
+  q->estats.partial = q->group_mode == EVQL_MODE_PARTIAL;
+  q->estats.rows = n;
   EmitArgs ea{};
+  PartialEmitPlan pplan;
   if (from_block) {
     // (plans that read first rows or count distinct values never arm the block)
     records_from_block(q, n, r.nwords);
@@ -517,6 +697,11 @@ static Status fetch_results(evql_query* q) {
     q->distinct_values.clear();
   } else if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea)) {
     st = emit_on_device(q, ea, r.d_rec, n, r.nwords);
+    if (!st.ok()) return st;
+    q->records.clear();
+    q->distinct_values.clear();
+  } else if (plan_partial_emit(partial_emit_input(q, n), &pplan) == PEMIT_DEVICE) {
+    st = emit_partial_on_device(q, pplan, r.d_rec, n, r.nwords);
     if (!st.ok()) return st;
     q->records.clear();
     q->distinct_values.clear();
@@ -532,6 +717,7 @@ static Status fetch_results(evql_query* q) {
     st = fetch_distinct_sets(q, n, r.nwords);
     if (!st.ok()) return st;
   }
+  q->estats.device_packed = q->demit.active;
   q->stats.num_groups = r.total;
   q->emit_pos = 0;
   q->executed = true;

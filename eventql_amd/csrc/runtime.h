@@ -460,6 +460,10 @@ struct evql_query {
     std::vector<uint64_t*> off;     // strings: pinned [n + 1] byte offsets
     std::vector<size_t> off_cap;
   } demit;
+  // EVQL_MODE_PARTIAL rows of large results take the same way: column 0 the keys (25 bytes
+  // each), column 1 the saved states (results.cc emit_partial_on_device)
+  bool partial_device_emit = true;  // EVQL_PARTIAL_DEVICE_EMIT, read when the operator is created
+  evql_emit_stats_t estats{};       // how the last fetched result left the device
   // EVQL_MODE_PARTIAL with count_distinct: the distinct values of every group, per
   // aggregate, read back from the HBM pair set; key = (identity, identity 2 | NULL flag)
   std::vector<std::map<std::pair<uint64_t, uint64_t>, std::vector<uint64_t>>> distinct_values;
@@ -646,6 +650,10 @@ Status bare_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, 
 Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n, int64_t limit,
                        uint64_t offset);
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
+// what plan_partial_emit (partial_emit_plan.h) decides on for a result of n groups of q
+PartialEmitInput partial_emit_input(const evql_query* q, uint64_t n);
+Status sha1_ranges_on_device(evql_ctx* ctx, const void* bytes, size_t len, const uint64_t* offsets,
+                             size_t n, uint8_t* out20);
 
 // chain_merge.cc / lsm.cc
 Status chain_merge(evql_query* head);

@@ -607,6 +607,28 @@ typedef struct {
 } evql_zone_stats_t;
 int evql_query_zone_stats(const evql_query_t* q, evql_zone_stats_t* out);
 
+/* How the last fetched result left the device.  Results of 65,536 groups and more are packed
+ * as SVector bytes by kernels and copied once into pinned memory; evql_query_next_batch then
+ * hands out slices in the order of the group records.  EVQL_MODE_FINAL: select lists of the
+ * group key, bare aggregates and first-row columns.  EVQL_MODE_PARTIAL: the (SHA-1 of the group
+ * tuple, saved states) rows of plans whose key is a bare column (or several, strings
+ * included), whose other select expressions are bare columns and whose aggregates are count,
+ * integer sums, fast float sums, min / max / mean; the environment variable
+ * EVQL_PARTIAL_DEVICE_EMIT=0, read when the query is created, keeps those rows on the host
+ * loop.  The bytes are the same either way.  EVQL_EARG before a result was fetched (the first
+ * evql_query_next_batch after an execute fetches it), and for a bare scan. */
+typedef struct {
+  uint32_t device_packed;      /* 1: packed by kernels; 0: by the host loop */
+  uint32_t partial;            /* 1: EVQL_MODE_PARTIAL rows */
+  uint64_t rows;               /* groups of the result */
+  uint64_t key_bytes;          /* PARTIAL, device-packed: bytes of the key column (25 per row) */
+  uint64_t data_bytes;         /* ... and of the data column; 0 otherwise */
+  uint32_t n_kernel_launches;  /* of the packing (0 on the host path) */
+  uint32_t n_host_waits;
+  double pack_ms;              /* device time from the first packing kernel to the last copy */
+} evql_emit_stats_t;
+int evql_query_emit_stats(const evql_query_t* q, evql_emit_stats_t* out);
+
 /* the generated HIP source of the fused kernel (inspection / tests) */
 const char* evql_query_kernel_source(const evql_query_t* q);
 
@@ -998,6 +1020,22 @@ int evql_compile_only(const evql_plan_desc_t* plan,
  * their source).  Default: the directory `_kcache` next to this shared library, shared by
  * every process that loads it; "" switches the disk cache off. */
 void evql_set_kernel_cache_dir(const char* dir);
+/* SHA-1 (FIPS 180) of n byte ranges on the device, with the kernel that hashes the group
+ * tuples of device-packed PARTIAL rows: range i is bytes[offsets[i], offsets[i + 1]),
+ * offsets has n + 1 entries, out20 receives n * 20 digest bytes.  It exists so that the
+ * kernel can be checked on its own (padding borders, empty and multi-block ranges).
+ * EVQL_EARG: a null argument (bytes may be NULL when len == 0, out20 when n == 0), offsets
+ * that decrease, or an offset beyond len. */
+int evql_ctx_sha1_ranges(evql_ctx_t* ctx, const void* bytes, size_t len, const uint64_t* offsets,
+                         size_t n, uint8_t* out20);
+/* Would a result of `n_groups` groups of `plan` leave as device-packed PARTIAL rows
+ * (evql_query_emit_stats)?  No device needed; columns as for evql_compile_only.  `merged`: the
+ * groups come out of an exchange or a chain merge.  *decision: 0 = yes, else why not
+ * (1 FINAL mode, 2 fewer than 65,536 groups, 3 EVQL_PARTIAL_DEVICE_EMIT=0, 4 a group
+ * expression or 5 a select expression that is not a bare column, 6 count_distinct / an exact
+ * float sum, 7 more than 32 columns, 8 a NIL-typed column, 9 a nested scan). */
+int evql_plan_partial_emit(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                           int ncolumns, uint64_t n_groups, int merged, int* decision);
 
 #ifdef __cplusplus
 }

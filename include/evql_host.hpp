@@ -159,6 +159,14 @@ class GpuGroupByScan : public TableExpression {
     return z;
   }
 
+  // how the last fetched result left the device (evql_query_emit_stats): throws before the
+  // first nextBatch behind an execute
+  evql_emit_stats_t emitStats() const {
+    evql_emit_stats_t e{};
+    if (evql_query_emit_stats(query_, &e) != EVQL_OK) throw std::runtime_error(evql_last_error());
+    return e;
+  }
+
   // Fuses LimitExpression(limit, offset, OrderByExpression(specs, this)) into the
   // operator (orderby.cc:60-160, limit.cc:52-125); limit < 0 = ORDER BY only.
   // Throws NotLowerable when the first sort key cannot be read on the device, in
