@@ -144,6 +144,10 @@ def lib():
     K.bind_chain_compact_sorted(L)
     K.bind_partial_emit(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
+    L.evql_merge_create_device.argtypes = [C.c_void_p, C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
+    L.evql_merge_stats.argtypes = [C.c_void_p, C.POINTER(K.MergeStats)]
+    L.evql_merge_index_frame.argtypes = [C.POINTER(K.PlanDesc), C.c_char_p, C.c_size_t,
+                                         C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
     L.evql_merge_destroy.argtypes = [C.c_void_p]
     L.evql_merge_add_frame.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.evql_merge_add_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p,
@@ -638,12 +642,24 @@ class LsmChain:
 
 class Merge:
     """mirrors csql::GroupByMergeExpression (groupby.cc:493-672) for partial
-    aggregates that arrive as bytes: add_frame()/add_rows(), then fetch_all()"""
+    aggregates that arrive as bytes: add_frame()/add_rows(), then fetch_all().
+    With a Context the rows are merged on its device (evql_merge_create_device);
+    a plan it does not take (count_distinct) raises EvqlError EVQL_ENOTSUP."""
 
-    def __init__(self, plan):
+    def __init__(self, plan, ctx=None):
         self.plan = plan
+        self.ctx = ctx  # (kept alive: the device merge runs on its stream)
         self.h = C.c_void_p()
-        _check(lib().evql_merge_create(C.byref(plan.desc), C.byref(self.h)))
+        if ctx is None:
+            _check(lib().evql_merge_create(C.byref(plan.desc), C.byref(self.h)))
+        else:
+            _check(lib().evql_merge_create_device(ctx.h, C.byref(plan.desc), C.byref(self.h)))
+
+    def stats(self):
+        """evql_merge_stats: a capi.MergeStats (all zero for a host merge)"""
+        st = K.MergeStats()
+        _check(lib().evql_merge_stats(self.h, C.byref(st)))
+        return st
 
     def add_frame(self, payload):
         buf = bytes(payload)
@@ -678,7 +694,21 @@ class Merge:
             self.h = None
 
     def __del__(self):
-        self.close()
+        # (a device merge is closed explicitly, like every object that holds device memory:
+        # no HIP call from the garbage collector, least of all while the interpreter exits)
+        if self.ctx is None:
+            self.close()
+
+
+def merge_index_frame(plan, payload):
+    """evql_merge_index_frame: the row offsets (rows + 1 of them) the device merge's host pass
+    finds in a QUERY_PARTIALAGGR_RESULT payload; raises EvqlError as Merge.add_frame would"""
+    buf = bytes(payload)
+    n = C.c_size_t()
+    _check(lib().evql_merge_index_frame(C.byref(plan.desc), buf, len(buf), None, 0, C.byref(n)))
+    off = (C.c_uint32 * max(1, n.value))()
+    _check(lib().evql_merge_index_frame(C.byref(plan.desc), buf, len(buf), off, n.value, C.byref(n)))
+    return list(off[:n.value])
 
 
 def _column_infos(columns):

@@ -177,6 +177,27 @@ class ZoneStats(C.Structure):
     ]
 
 
+class MergeStats(C.Structure):
+    """evql_merge_stats_t"""
+    _fields_ = [
+        ("on_device", C.c_uint32),
+        ("packed_on_device", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("rows_added", C.c_uint64),
+        ("rows_pending", C.c_uint64),
+        ("groups", C.c_uint64),
+        ("compactions", C.c_uint64),
+        ("sort_passes", C.c_uint64),
+        ("prefix_collisions", C.c_uint64),
+        ("full_key_sorts", C.c_uint64),
+        ("device_bytes", C.c_uint64),
+        ("host_index_ms", C.c_double),
+        ("upload_ms", C.c_double),
+        ("merge_ms", C.c_double),
+        ("pack_ms", C.c_double),
+    ]
+
+
 class EmitStats(C.Structure):
     """evql_emit_stats_t"""
     _fields_ = [

@@ -4167,4 +4167,282 @@ hipError_t launch_cmp_permute(const CmpPermuteArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- merge of PARTIAL rows that arrive as bytes (merge_device.cc) -----------
+namespace {
+
+// Bytes of an indexed row.  The host validated every row (merge_frame_index.cc); `end` -- the
+// row's end -- still bounds every load, so that a read behind it yields zero bytes instead of
+// another row's.
+__device__ __forceinline__ u64 mrg_le(const u8* d, u64 p, u64 end, u32 nbytes) {
+  u64 v = 0;
+  for (u32 k = 0; k < nbytes; ++k) {
+    if (p + k < end) v |= (u64) d[p + k] << (8 * k);
+  }
+  return v;
+}
+__device__ __forceinline__ u64 mrg_varuint(const u8* d, u64* p, u64 end) {
+  u64 v = 0;
+  for (u32 i = 0; i < 10; ++i) {
+    const u8 b = *p < end ? d[*p] : (u8) 0;
+    ++*p;
+    v |= (u64) (b & 0x7f) << (7 * i);
+    if (!(b & 0x80)) break;
+  }
+  return v;
+}
+
+// one thread per row: instance_loadstate of every aggregate, SValue::decode of every other cell
+__global__ void __launch_bounds__(kBlock) k_mrg_decode(MrgDecodeArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    const u64 koff = a.key_off[i];
+    u64 p, end;
+    if (a.data_off) {
+      p = a.data_off[i];
+      end = a.data_end[i];
+    } else {
+      p = koff + kMergeKeyBytes;
+      end = a.key_off[i + 1];
+    }
+    u64* rec = (u64*) a.records + i * a.L.rw;
+    rec[0] = mrg_le(a.keys, koff, koff + kMergeKeyBytes, 8);
+    rec[1] = mrg_le(a.keys, koff + 8, koff + kMergeKeyBytes, 8);
+    rec[2] = mrg_le(a.keys, koff + 16, koff + kMergeKeyBytes, 4);
+    for (u32 c = 0; c < a.L.ncols; ++c) {
+      u64* w = rec + a.L.word[c];
+      switch (a.L.cls[c]) {
+        case MCELL_VARUINT:
+          w[0] = mrg_varuint(a.data, &p, end);
+          break;
+        case MCELL_RAW8:
+          w[0] = mrg_le(a.data, p, end, 8);
+          p += 8;
+          break;
+        case MCELL_COUNT_RAW8:
+          w[1] = mrg_varuint(a.data, &p, end);
+          w[0] = mrg_le(a.data, p, end, 8);
+          p += 8;
+          break;
+        default: {
+          const u32 type = (u32) mrg_le(a.data, p, end, 1);
+          ++p;
+          const u64 n = mrg_varuint(a.data, &p, end);
+          u64 val = 0;
+          u32 tag = n ? (u32) mrg_le(a.data, p + n - 1, end, 1) : (u32) kStagNull;
+          if (type == kMergeWireBool) {
+            val = mrg_le(a.data, p, end, 1);
+          } else if (type == kMergeWireString) {
+            val = (mrg_le(a.data, p, end, 4) << 40) | ((a.arena_pos + p + 4) & kStrOffMask);
+          } else if (type != kMergeWireNil) {
+            val = mrg_le(a.data, p, end, 8);
+          }
+          w[0] = val;
+          w[1] = (u64) type | ((u64) tag << 8);
+          p += n;
+        }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_gather_key(const u64* records, u32 rw, u32 word,
+                                                           const u32* perm, u64 n, u64* out) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < n; i += (u64) gridDim.x * kBlock) {
+    const u64 r = perm ? perm[i] : i;
+    out[i] = r < n ? records[r * rw + word] : 0ull;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_heads(const u64* records, u32 rw, const u32* perm,
+                                                      u64 n, u8* flags, u64* heads, u64* counters) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < n; i += (u64) gridDim.x * kBlock) {
+    bool head = true;
+    if (i) {
+      const u64 r = perm[i], q = perm[i - 1];
+      if (r < n && q < n) {
+        const u64* a = records + r * rw;
+        const u64* b = records + q * rw;
+        head = a[0] != b[0] || a[1] != b[1] || a[2] != b[2];
+        if (head && a[0] == b[0]) atomicAdd((unsigned long long*) &counters[0], 1ull);
+      }
+    }
+    flags[i] = head;
+    heads[i] = head;
+  }
+}
+
+// (w, cnt) += (ow, ocnt): instance_merge of merge.cc merge_state / fold_minmax
+__device__ __forceinline__ void mrg_fold_cell(u32 op, u64* w, u64* cnt, u64 ow, u64 ocnt) {
+  switch (op) {
+    case MFOLD_ADD_U64: *w += ow; return;
+    case MFOLD_ADD_F64: *w = evql_f64_bits(evql_as_f64(*w) + evql_as_f64(ow)); return;
+    case MFOLD_MEAN:
+      *w = evql_f64_bits(evql_as_f64(*w) + evql_as_f64(ow));
+      *cnt += ocnt;
+      return;
+    case MFOLD_LAST:
+      *w = ow;
+      *cnt = ocnt;
+      return;
+  }
+  if (ocnt == 0) return;
+  bool take = *cnt == 0;
+  if (!take) {
+    switch (op) {
+      case MFOLD_MIN_U64: take = ow < *w; break;
+      case MFOLD_MAX_U64: take = ow > *w; break;
+      case MFOLD_MIN_I64: take = (i64) ow < (i64) *w; break;
+      case MFOLD_MAX_I64: take = (i64) ow > (i64) *w; break;
+      case MFOLD_MIN_F64: take = evql_as_f64(ow) < evql_as_f64(*w); break;
+      default: take = evql_as_f64(ow) > evql_as_f64(*w);
+    }
+  }
+  if (take) *w = ow;
+  *cnt += ocnt;
+}
+
+// The thread of a head folds its group: rows i .. (next head - 1) in perm order -- the merged
+// group first, then the pending rows as they arrived -- cell by cell from the zero state.
+__global__ void __launch_bounds__(kBlock) k_mrg_fold(MrgFoldArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    if (!a.flags[i]) continue;
+    const u64 g = a.seg[i];
+    const u64 first = a.perm[i];
+    if (g >= a.out_cap || first >= a.n) continue;
+    u64* out = (u64*) a.out + g * a.L.rw;
+    const u64* in0 = (const u64*) a.records + first * a.L.rw;
+    out[0] = in0[0];
+    out[1] = in0[1];
+    out[2] = in0[2];
+    for (u32 c = 0; c < a.L.ncols; ++c) {
+      const u32 op = a.L.op[c], word = a.L.word[c];
+      const bool two = a.L.cls[c] != MCELL_VARUINT && a.L.cls[c] != MCELL_RAW8;
+      u64 w = 0, cnt = 0;
+      for (u64 j = i; j < a.n && (j == i || !a.flags[j]); ++j) {
+        const u64 r = a.perm[j];
+        if (r >= a.n) continue;
+        const u64* in = (const u64*) a.records + r * a.L.rw + word;
+        mrg_fold_cell(op, &w, &cnt, in[0], two ? in[1] : 0ull);
+      }
+      out[word] = w;
+      if (two) out[word + 1] = cnt;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_str_sizes(MrgStrArgs a) {
+  const u64 total = a.n * a.nstr;
+  for (u64 e = (u64) blockIdx.x * kBlock + threadIdx.x; e < total; e += (u64) gridDim.x * kBlock) {
+    const u64 g = e / a.nstr;
+    const u32 s = (u32) (e - g * a.nstr);
+    a.sizes[e] = a.records[g * a.rw + a.word[s]] >> 40;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_str_copy(MrgStrArgs a) {
+  const u64 total = a.n * a.nstr;
+  for (u64 e = (u64) blockIdx.x * kBlock + threadIdx.x; e < total; e += (u64) gridDim.x * kBlock) {
+    const u64 g = e / a.nstr;
+    const u32 s = (u32) (e - g * a.nstr);
+    u64* wp = (u64*) a.records + g * a.rw + a.word[s];
+    const u64 len = *wp >> 40, pos = *wp & kStrOffMask, off = a.sizes[e];
+    for (u64 k = 0; k < len; ++k) {
+      if (pos + k < a.src_len && off + k < a.dst_cap) a.dst[off + k] = a.src[pos + k];
+    }
+    *wp = (len << 40) | (off & kStrOffMask);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_cell_fixed(MrgCellArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    const u64* w = (const u64*) a.records + i * a.rw + a.word;
+    const u8 tag = (u8) (w[1] >> 8);
+    if ((i + 1) * a.elem > a.out_cap) continue;
+    if (a.elem == 2) {  // BOOL: value byte, tag byte
+      a.out[i * 2] = (u8) (w[0] != 0);
+      a.out[i * 2 + 1] = tag;
+    } else {
+      emit_store9(a.out, i, w[0], tag);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_cell_str_sizes(MrgCellArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    a.offsets[i] = 5 + (a.records[i * a.rw + a.word] >> 40);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mrg_cell_str_bytes(MrgCellArgs a) {
+  for (u64 i = (u64) blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (u64) gridDim.x * kBlock) {
+    const u64* w = (const u64*) a.records + i * a.rw + a.word;
+    const u32 len = (u32) (w[0] >> 40);
+    const u64 pos = w[0] & kStrOffMask, off = a.offsets[i];
+    if (off + 5 + len > a.out_cap) continue;
+    u8* p = a.out + off;
+    p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
+    for (u32 k = 0; k < len; ++k) p[4 + k] = pos + k < a.arena_len ? a.arena[pos + k] : (u8) 0;
+    p[4 + len] = (u8) (w[1] >> 8);
+  }
+}
+
+}  // namespace
+
+hipError_t launch_mrg_decode(const MrgDecodeArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_decode, dim3(grid_for(a.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_gather_key(const uint64_t* records, uint32_t rw, uint32_t word,
+                                 const uint32_t* perm, uint64_t n, uint64_t* out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_gather_key, dim3(grid_for(n)), dim3(kBlock), 0, s, (const u64*) records, rw,
+                     word, perm, (u64) n, (u64*) out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_heads(const uint64_t* records, uint32_t rw, const uint32_t* perm, uint64_t n,
+                            uint8_t* flags, uint64_t* heads, uint64_t* counters, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_heads, dim3(grid_for(n)), dim3(kBlock), 0, s, (const u64*) records, rw, perm,
+                     (u64) n, flags, (u64*) heads, (u64*) counters);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_fold(const MrgFoldArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_fold, dim3(grid_for(a.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_str_sizes(const MrgStrArgs& a, hipStream_t s) {
+  if (a.n == 0 || a.nstr == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_str_sizes, dim3(grid_for(a.n * a.nstr)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_str_copy(const MrgStrArgs& a, hipStream_t s) {
+  if (a.n == 0 || a.nstr == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_str_copy, dim3(grid_for(a.n * a.nstr)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_cell_fixed(const MrgCellArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_cell_fixed, dim3(grid_for(a.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_cell_str_sizes(const MrgCellArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_cell_str_sizes, dim3(grid_for(a.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_mrg_cell_str_bytes(const MrgCellArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mrg_cell_str_bytes, dim3(grid_for(a.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace evql

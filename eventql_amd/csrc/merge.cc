@@ -9,15 +9,18 @@
 //
 // This is the coordinator's side of the exchange for partial aggregates that
 // arrive as bytes (from evql_query_next_batch in EVQL_MODE_PARTIAL on another
-// node, or from an unmodified reference node): its work is O(groups x frames) of
-// sequential LEB128 decoding, not a scan, so it stays on the host.  Partial
-// tables that live on other GPUs are merged on the device instead
-// (evql_query_import_groups).
+// node, or from an unmodified reference node).  This file is the host merge: a
+// hash map of groups fed row by row, and the only one that unions count_distinct
+// sets.  A handle made by evql_merge_create_device carries a MergeDevice instead
+// (merge_device.cc: validate, upload, decode, sort, fold and pack on the device)
+// and every call below hands over to it.  Partial tables that live on other GPUs
+// are merged with evql_query_import_groups.
 #include <cstring>
 #include <map>
 #include <memory>
 #include <set>
 #include <unordered_map>
+#include "merge_device.h"
 #include "plan_ir.h"
 #include "runtime.h"
 
@@ -81,9 +84,19 @@ struct evql_merge {
   bool iterating = false;
   uint64_t frames = 0, rows = 0;
   std::vector<std::vector<uint8_t>> out_cols;
+  MergeDevice* dev = nullptr;  // evql_merge_create_device: the state lives there
+  ~evql_merge() { merge_device_destroy(dev); }
 };
 
 namespace {
+
+// a call on a device merge: its context's device, then the Status as a return code
+template <typename F>
+int on_device(evql_merge* m, F f) {
+  if (hipSetDevice(merge_device_ordinal(m->dev)) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  Status st = f();
+  return st.ok() ? EVQL_OK : fail(st.code, st.msg);
+}
 
 // instance_loadstate, inverse of save_state() in results.cc
 bool load_state(uint32_t fn, Reader* r, Cell* c) {
@@ -295,10 +308,53 @@ int evql_merge_create(const evql_plan_desc_t* plan, evql_merge_t** out) {
   return EVQL_OK;
 }
 
+int evql_merge_create_device(evql_ctx_t* ctx, const evql_plan_desc_t* plan, evql_merge_t** out) {
+  if (!ctx || !plan || !out) return fail(EVQL_EARG, "null argument");
+  int rc = evql_merge_create(plan, out);
+  if (rc != EVQL_OK) return rc;
+  std::unique_ptr<evql_merge> m(*out);
+  *out = nullptr;
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  Status st = merge_device_create(ctx, m->select, &m->dev);
+  if (!st.ok()) return fail(st.code, st.msg);
+  *out = m.release();
+  return EVQL_OK;
+}
+
+int evql_merge_index_frame(const evql_plan_desc_t* plan, const void* payload, size_t len,
+                           uint32_t* row_off, size_t cap, size_t* n_off) {
+  if (!plan || (!payload && len) || !n_off) return fail(EVQL_EARG, "null argument");
+  evql_merge_t* m = nullptr;
+  int rc = evql_merge_create(plan, &m);
+  if (rc != EVQL_OK) return rc;
+  std::unique_ptr<evql_merge> hold(m);
+  MergeRecordLayout L;
+  if (merge_record_layout(m->select, &L) != MLAYOUT_OK) {
+    return fail(EVQL_ENOTSUP, "device merge: select list not taken");
+  }
+  std::vector<uint32_t> off;
+  switch (index_merge_frame(L, static_cast<const uint8_t*>(payload), len, &off)) {
+    case MINDEX_OK: break;
+    case MINDEX_MALFORMED: return fail(EVQL_EIO, "invalid partialaggr result encoding");
+    default: return fail(EVQL_ENOTSUP, "device merge: frame not taken");
+  }
+  *n_off = off.size();
+  if (row_off) memcpy(row_off, off.data(), std::min(cap, off.size()) * 4);
+  return EVQL_OK;
+}
+
+int evql_merge_stats(const evql_merge_t* m, evql_merge_stats_t* out) {
+  if (!m || !out) return fail(EVQL_EARG, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (m->dev) merge_device_stats(m->dev, out);
+  return EVQL_OK;
+}
+
 void evql_merge_destroy(evql_merge_t* m) { delete m; }
 
 int evql_merge_add_frame(evql_merge_t* m, const void* payload, size_t len) {
   if (!m || (!payload && len)) return fail(EVQL_EARG, "null argument");
+  if (m->dev) return on_device(m, [&] { return merge_device_add_frame(m->dev, payload, len); });
   Reader r{static_cast<const uint8_t*>(payload), len};
   r.varuint();  // flags
   const uint64_t count = r.varuint();
@@ -312,6 +368,9 @@ int evql_merge_add_frame(evql_merge_t* m, const void* payload, size_t len) {
 int evql_merge_add_rows(evql_merge_t* m, const void* keys, size_t keys_len, const void* data,
                         size_t data_len, size_t nrows) {
   if (!m) return fail(EVQL_EARG, "null argument");
+  if (m->dev) {
+    return on_device(m, [&] { return merge_device_add_rows(m->dev, keys, keys_len, data, data_len, nrows); });
+  }
   // two STRING SVectors (u32 len, bytes, tag per element), as PartialGroupBy's
   // nextBatch hands them to its parent (groupby.cc:438-472)
   Reader kr{static_cast<const uint8_t*>(keys), keys_len};
@@ -337,7 +396,15 @@ int evql_merge_add_rows(evql_merge_t* m, const void* keys, size_t keys_len, cons
   return EVQL_OK;
 }
 
-uint64_t evql_merge_num_groups(const evql_merge_t* m) { return m->groups.size(); }
+uint64_t evql_merge_num_groups(const evql_merge_t* m) {
+  if (m->dev) {
+    // (the pending rows are folded first; an error is left in evql_last_error)
+    uint64_t n = 0;
+    on_device(const_cast<evql_merge_t*>(m), [&] { return merge_device_num_groups(m->dev, &n); });
+    return n;
+  }
+  return m->groups.size();
+}
 size_t evql_merge_column_count(const evql_merge_t* m) { return m->select.size(); }
 uint32_t evql_merge_column_type(const evql_merge_t* m, size_t idx) {
   return idx < m->select.size() ? m->select[idx].return_type : uint32_t(EVQL_T_NIL);
@@ -346,6 +413,7 @@ uint32_t evql_merge_column_type(const evql_merge_t* m, size_t idx) {
 int evql_merge_next_batch(evql_merge_t* m, size_t max_rows, evql_column_buf_t* cols,
                           size_t* nrows) {
   if (!m || !cols || !nrows) return fail(EVQL_EARG, "null argument");
+  if (m->dev) return on_device(m, [&] { return merge_device_next_batch(m->dev, max_rows, cols, nrows); });
   if (!m->iterating) {
     m->it = m->groups.begin();
     m->iterating = true;

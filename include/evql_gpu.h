@@ -810,6 +810,47 @@ uint32_t evql_merge_column_type(const evql_merge_t* m, size_t idx);
 int evql_merge_next_batch(evql_merge_t* m, size_t max_rows,
                           evql_column_buf_t* cols, size_t* nrows);
 
+/*
+ * The same merge on the device of `ctx`: every call above works on the
+ * handle.  add_frame / add_rows validate the bytes on the host, upload them once and decode the
+ * rows into fixed-width records; the groups are folded -- a stable sort by key, one fold per
+ * group, in arrival order, so float sums come out bit for bit as on the host -- when
+ * num_groups / next_batch ask for them, and as soon as more than EVQL_MERGE_PENDING_ROWS rows
+ * (read here, default 2^24) wait to be folded.  Results of 65,536 groups and more are packed
+ * on the device.  Output order is the sorted key order.
+ *   Select expressions: count, sum, min, max, mean (bare or inside an expression, which is
+ *   evaluated on the host over the merged state) and non-aggregates of every SValue type.
+ *   EVQL_ENOTSUP for count_distinct (its state is a set): create the host merge then.
+ * Differences from the host merge: a frame is added whole or not at all (the host merge keeps
+ * the rows in front of a malformed one); a non-aggregate cell that is not NIL and not of the
+ * size class of its program's return type (STRING / BOOL / the 8-byte numerics) rejects the
+ * frame with EVQL_ENOTSUP, as does a string of 2^24 bytes or more, a frame of 4 GiB or more
+ * and more than 2^32 - 1 resident rows (groups + rows not yet folded); a varuint longer than
+ * ten bytes is malformed.
+ */
+int evql_merge_create_device(evql_ctx_t* ctx, const evql_plan_desc_t* plan, evql_merge_t** out);
+typedef struct {
+  uint32_t on_device;         /* 0: a host merge, every other field is 0 */
+  uint32_t packed_on_device;  /* the last fetch: 1 = packed by kernels, 0 = by the host loop */
+  uint64_t frames;            /* add_frame calls that succeeded */
+  uint64_t rows_added;
+  uint64_t rows_pending;      /* decoded, not yet folded */
+  uint64_t groups;            /* as of the last fold */
+  uint64_t compactions;       /* folds so far (eager and lazy) */
+  uint64_t sort_passes;       /* 8-bit digit passes of all folds */
+  uint64_t prefix_collisions; /* neighbours with equal first 8 key bytes and different keys */
+  uint64_t full_key_sorts;    /* folds that therefore sorted by all 20 bytes */
+  uint64_t device_bytes;      /* records + arena held now */
+  double host_index_ms, upload_ms, merge_ms, pack_ms; /* host clock; pack_ms: the last fetch */
+} evql_merge_stats_t;
+int evql_merge_stats(const evql_merge_t* m, evql_merge_stats_t* out);
+/* The host pass of add_frame on a device merge, on its own (no device needed): validates
+ * `payload` against plan->select_exprs and writes up to `cap` of its rows + 1 row offsets
+ * (row i = payload[row_off[i], row_off[i + 1]), the key first) to row_off (may be NULL);
+ * *n_off = rows + 1.  EVQL_EIO / EVQL_ENOTSUP as add_frame answers them. */
+int evql_merge_index_frame(const evql_plan_desc_t* plan, const void* payload, size_t len,
+                           uint32_t* row_off, size_t cap, size_t* n_off);
+
 /* ------------------------------------------------------------------------ */
 /* ORDER BY .. LIMIT above the GROUP BY                                       */
 /*   OrderByExpression  sql/statements/select/orderby.cc:60-160               */

@@ -203,12 +203,12 @@ class GpuGroupByScan : public TableExpression {
 class GroupByMerge : public TableExpression {
  public:
   explicit GroupByMerge(const evql_plan_desc_t& plan) : merge_(nullptr) {
-    int rc = evql_merge_create(&plan, &merge_);
-    if (rc == EVQL_ENOTSUP) throw NotLowerable(evql_last_error());
-    if (rc != EVQL_OK) throw std::runtime_error(evql_last_error());
-    const size_t n = evql_merge_column_count(merge_);
-    for (size_t i = 0; i < n; ++i) types_.push_back(SType(evql_merge_column_type(merge_, i)));
-    bufs_.resize(types_.size());
+    init(evql_merge_create(&plan, &merge_));
+  }
+  // the merge on the device of `ctx` (evql_merge_create_device); NotLowerable for a select
+  // list it does not take (count_distinct): construct the host merge then
+  GroupByMerge(evql_ctx_t* ctx, const evql_plan_desc_t& plan) : merge_(nullptr) {
+    init(evql_merge_create_device(ctx, &plan, &merge_));
   }
   ~GroupByMerge() override { evql_merge_destroy(merge_); }
   GroupByMerge(const GroupByMerge&) = delete;
@@ -250,7 +250,21 @@ class GroupByMerge : public TableExpression {
   size_t getColumnCount() const override { return types_.size(); }
   SType getColumnType(size_t idx) const override { return types_.at(idx); }
 
+  // evql_merge_stats: what a device merge did (all zero for a host merge)
+  evql_merge_stats_t mergeStats() const {
+    evql_merge_stats_t st;
+    evql_merge_stats(merge_, &st);
+    return st;
+  }
+
  private:
+  void init(int rc) {
+    if (rc == EVQL_ENOTSUP) throw NotLowerable(evql_last_error());
+    if (rc != EVQL_OK) throw std::runtime_error(evql_last_error());
+    const size_t n = evql_merge_column_count(merge_);
+    for (size_t i = 0; i < n; ++i) types_.push_back(SType(evql_merge_column_type(merge_, i)));
+    bufs_.resize(types_.size());
+  }
   evql_merge_t* merge_;
   std::vector<SType> types_;
   std::vector<evql_column_buf_t> bufs_;
