@@ -427,9 +427,37 @@ struct Gen {
 
   // evaluates row (u, j) of the loaded tile into `o` (columns outside `only` were not
   // loaded and read as 0: the caller knows that the row function does not use them)
-  void eval_call(const char* ind, int j, const std::vector<bool>* only = nullptr) {
-    s << ind << "evql_eval_row(A, r + " << j << ", (r + " << j << " >= A.row_begin) && (r + " << j
-      << " < A.row_end)";
+  //
+  // Whether the row lies in the plan's window [A.row_begin, A.row_end) is decided in 32 bits.
+  // Once per tile, on uniform values (tile_window, after `base`): the window clipped to the
+  // tile as offsets wlo <= whi into it, its length `wlen`, and per lane `wrel` = the offset of
+  // the lane's first row of step 0, minus wlo.  Row (u, j) has the offset
+  // (u * BLOCK + tid) * 2 + j, so per row one add of a constant and one unsigned compare
+  // remain: offsets below wlo wrap to >= 2^32 - TILE_ROWS > wlen.  (The two 64-bit compares
+  // of r + j against the window cost 8 .. 15 VGPRs in the narrow shapes.)  Every tile loop
+  // numbers its rows this way.
+  // Loops that hold few values per lane keep the 64-bit compares (window32 = false): the
+  // predicate-only passes evql_scan_count and evql_part_count and the ungrouped scan came out
+  // 1 .. 5 VGPRs FATTER in the 32-bit form over plain pages, against their pins.
+  bool window32 = true;
+  void tile_window(const char* ind) {
+    if (!window32) return;
+    s << ind << "const u64 wb = A.row_begin > base ? A.row_begin - base : 0ull;\n";
+    s << ind << "const u64 we = A.row_end > base ? A.row_end - base : 0ull;\n";
+    s << ind << "const u32 wlo = (u32) (wb < (u64) EVQL_TILE_ROWS ? wb : (u64) EVQL_TILE_ROWS);\n";
+    s << ind << "const u32 whi = (u32) (we < (u64) EVQL_TILE_ROWS ? we : (u64) EVQL_TILE_ROWS);\n";
+    s << ind << "const u32 wlen = whi > wlo ? whi - wlo : 0u;\n";
+    s << ind << "const u32 wrel = 2u * tid - wlo;\n";
+  }
+  void eval_call(const char* ind, int j, const std::vector<bool>* only = nullptr,
+                 const char* out = "o") {
+    if (window32) {
+      s << ind << "evql_eval_row(A, r + " << j << ", wrel + (u32) (u * EVQL_BLOCK * 2 + " << j
+        << ") < wlen";
+    } else {
+      s << ind << "evql_eval_row(A, r + " << j << ", (r + " << j << " >= A.row_begin) && (r + " << j
+        << " < A.row_end)";
+    }
     for (int i = 0; i < NC; ++i) {
       if (only && !(*only)[i]) {
         s << ", 0ull, 0u";
@@ -437,10 +465,12 @@ struct Gen {
       }
       s << ", x" << i << "[u][" << j << "], y" << i << "[u][" << j << "]";
     }
-    s << ", o);\n";
+    s << ", " << out << ");\n";
   }
 
   // ---- the fused scan kernel --------------------------------------------------------
+  // (the tile loop reads the identity slots of a step's two rows ahead of their updates)
+  bool probe_ahead() const { return grouped && S > 0 && !kp.has_ident2(); }
   void scan_kernel() {
     s << "struct EvqlAcc {\n  u64 passed;\n  u64 spilled;\n";
     if (!grouped) s << "  u64 w[" << (NW > 0 ? NW : 1) << "];\n";
@@ -479,7 +509,8 @@ struct Gen {
     // lane of the wave reaches the cooperative part together.
     s << "__device__ __forceinline__ void evql_update(const EvqlArgs& A, u64* lds, EvqlAcc& acc,\n"
          "                                            const bool bypass, const u64 row, "
-         "const EvqlRowOut& o) {\n";
+         "const EvqlRowOut& o"
+      << (probe_ahead() ? ", const u64 slot0" : "") << ") {\n";
     s << "  acc.passed += o.live ? 1 : 0;\n";
     if (!grouped) {
       if (kp.need_first_row) s << "  if (o.live && row < acc.first) acc.first = row;\n";
@@ -512,8 +543,9 @@ struct Gen {
           s << "    else s = evql_lds_find2<16>(lds, lds + EVQL_LSTRIDE, EVQL_LDS_SLOTS - 1, o.ident, "
                "o.ident2, (u32) evql_mix64(o.ident));\n";
         } else {
-          s << "    else s = evql_lds_find<16>(lds, EVQL_LDS_SLOTS - 1, o.ident, (u32) "
-               "evql_mix64(o.ident));\n";
+          s << "    else s = evql_lds_find" << (probe_ahead() ? "_from" : "")
+            << "<16>(lds, EVQL_LDS_SLOTS - 1, o.ident, (u32) evql_mix64(o.ident)"
+            << (probe_ahead() ? ", slot0" : "") << ");\n";
         }
         s << "    if (s < 0) atomicAdd(reinterpret_cast<u32*>(&lds[EVQL_WORDS * EVQL_LSTRIDE]), 1u);\n";
         s << "  }\n";
@@ -526,41 +558,70 @@ struct Gen {
         // two-group plan -- and no scalar round trips in front of every row.  Plans with
         // 2 .. 4 expected groups keep EVQL_LCACHE = 4 entries, enough to hold every group
         // (predicated updates: no dynamic register indexing).
-        s << "  if (s >= 0) {\n";
-        s << "    bool hit = false;\n";
-        for (int j = 0; j < kp.lane_cache; ++j) {
-          s << "    {\n      const bool h = acc.cs[" << j << "] == s;\n      hit = hit || h;\n";
-          if (kp.need_first_row) {
-            s << "      acc.cfirst[" << j << "] = (h && row < acc.cfirst[" << j << "]) ? row : acc.cfirst["
-              << j << "];\n";
-          }
+        //
+        // One entry (every plan but those with 2 .. 4 expected groups): the same policy and
+        // the same LDS atomics, as two branches.  The select form ran both halves for every
+        // row -- combines and selects that picked nothing, the entry refilled with
+        // identities and overwritten at once -- and with 1000 spread groups, where a lane's
+        // entry practically never hits, that was 40 % of the vector instructions of a passing
+        // row.  The miss block holds atomics and stays a branch; its install is plain moves
+        // under the exec mask.  The hit block is five instructions, which the back end would
+        // rather run with an empty exec mask than jump over: the empty asm statement makes it
+        // keep the s_cbranch_execz.
+        if (kp.lane_cache == 1) {
+          s << "  const bool hit = s >= 0 && acc.cs[0] == s;\n";
+          s << "  const bool miss = s >= 0 && !hit;\n";
+          s << "  if (hit) {\n    asm volatile(\"\");\n";
+          if (kp.need_first_row) s << "    if (row < acc.cfirst[0]) acc.cfirst[0] = row;\n";
           for (int i = 0; i < U(); ++i) {
-            s << "      if (h && o.uc[" << i << "]) acc.cw[" << j << "][" << i << "] = evql_combine<"
-              << op_name(updw[i].op) << ">(acc.cw[" << j << "][" << i << "], o.ub[" << i << "]);\n";
+            s << "    if (o.uc[" << i << "]) acc.cw[0][" << i << "] = evql_combine<" << op_name(updw[i].op)
+              << ">(acc.cw[0][" << i << "], o.ub[" << i << "]);\n";
           }
-          s << "    }\n";
-        }
-        // (the victim is chosen with selects, entry by entry: an if / else-if chain over
-        // acc.cv is turned into an indexed access by the optimiser, which puts the
-        // accumulators into scratch memory)
-        s << "    if (!hit) {\n";
-        for (int j = 0; j < kp.lane_cache; ++j) {
-          s << "      {\n        const bool v = acc.cv == " << j << "u;\n";
-          s << "        if (v && acc.cs[" << j << "] >= 0) evql_flush_entry<" << j << ">(lds, acc);\n";
-          s << "        acc.cs[" << j << "] = v ? s : acc.cs[" << j << "];\n";
-          if (kp.need_first_row) {
-            s << "        acc.cfirst[" << j << "] = v ? row : acc.cfirst[" << j << "];\n";
+          s << "  }\n";
+          s << "  if (miss) {\n";
+          s << "    if (acc.cs[0] >= 0) evql_flush_entry<0>(lds, acc);\n";
+          s << "    acc.cs[0] = s;\n";
+          if (kp.need_first_row) s << "    acc.cfirst[0] = row;\n";
+          // (a skipped update carries the identity of its op in o.ub[])
+          for (int i = 0; i < U(); ++i) s << "    acc.cw[0][" << i << "] = o.ub[" << i << "];\n";
+          s << "  }\n";
+        } else {
+          s << "  if (s >= 0) {\n";
+          s << "    bool hit = false;\n";
+          for (int j = 0; j < kp.lane_cache; ++j) {
+            s << "    {\n      const bool h = acc.cs[" << j << "] == s;\n      hit = hit || h;\n";
+            if (kp.need_first_row) {
+              s << "      acc.cfirst[" << j << "] = (h && row < acc.cfirst[" << j << "]) ? row : acc.cfirst["
+                << j << "];\n";
+            }
+            for (int i = 0; i < U(); ++i) {
+              s << "      if (h && o.uc[" << i << "]) acc.cw[" << j << "][" << i << "] = evql_combine<"
+                << op_name(updw[i].op) << ">(acc.cw[" << j << "][" << i << "], o.ub[" << i << "]);\n";
+            }
+            s << "    }\n";
           }
-          for (int i = 0; i < U(); ++i) {
-            s << "        acc.cw[" << j << "][" << i << "] = (v && o.uc[" << i << "]) ? o.ub[" << i
-              << "] : acc.cw[" << j << "][" << i << "];\n";
+          // (the victim is chosen with selects, entry by entry: an if / else-if chain over
+          // acc.cv is turned into an indexed access by the optimiser, which puts the
+          // accumulators into scratch memory)
+          s << "    if (!hit) {\n";
+          for (int j = 0; j < kp.lane_cache; ++j) {
+            s << "      {\n        const bool v = acc.cv == " << j << "u;\n";
+            s << "        if (v && acc.cs[" << j << "] >= 0) evql_flush_entry<" << j << ">(lds, acc);\n";
+            s << "        acc.cs[" << j << "] = v ? s : acc.cs[" << j << "];\n";
+            if (kp.need_first_row) {
+              s << "        acc.cfirst[" << j << "] = v ? row : acc.cfirst[" << j << "];\n";
+            }
+            for (int i = 0; i < U(); ++i) {
+              s << "        acc.cw[" << j << "][" << i << "] = (v && o.uc[" << i << "]) ? o.ub[" << i
+                << "] : acc.cw[" << j << "][" << i << "];\n";
+            }
+            s << "      }\n";
           }
-          s << "      }\n";
+          if (kp.lane_cache > 1) {
+            s << "      acc.cv = (acc.cv + 1u) & " << (kp.lane_cache - 1) << "u;\n";
+          }
+          s << "    }\n  }\n";
         }
-        if (kp.lane_cache > 1) {
-          s << "      acc.cv = (acc.cv + 1u) & " << (kp.lane_cache - 1) << "u;\n";
-        }
-        s << "    }\n  }\n";
         s << "  const bool spill = o.live && s < 0;\n";
         s << "  acc.spilled += spill ? 1 : 0;\n";
       } else {
@@ -663,6 +724,7 @@ struct Gen {
       if (kp.need_first_row) s << "  acc.first = 0xFFFFFFFFFFFFFFFFull;\n";
     }
     zone_skip_decl("  ");
+    window32 = grouped;
     tile_loop_twice("  ", [&] {
     s << "  u32 tile_no = 0;\n";
     s << "  for (u64 t = blockIdx.x; t < A.ntiles; t += gridDim.x, ++tile_no) {\n";
@@ -682,9 +744,14 @@ struct Gen {
       s << "    const bool bypass = false;\n";
     }
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     // (SQ counters, round 2: 55-62 % of the wave cycles of every variant of this kernel are
     // s_waitcnt stalls, VALU 6-11 %, LDS <= 14 % -- each wave drains its memory pipeline at
-    // the tile border.  Refilling a step's registers with the next tile's rows right after
+    // the tile border.  These are shares of WAVE cycles, summed over the four waves that
+    // share a SIMD here (one 1024-thread workgroup per CU): a SIMD's VALU issue is busy four
+    // times that share of its time -- 71 % for today's config 3 at 18 %, DESIGN.md 6m -- so
+    // the instructions per row behind the loads do count.  Refilling a step's registers
+    // with the next tile's rows right after
     // the step is evaluated (a ring over the unroll steps) was tried and ran 1.2-2.7x
     // SLOWER, conditional or not: across the back edge of the tile loop the compiler's
     // waitcnt insertion no longer knows how many loads are outstanding and emits
@@ -697,13 +764,29 @@ struct Gen {
     tile_loads("    ");
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
-    s << "      EvqlRowOut o;\n";
-    for (int j = 0; j < 2; ++j) {
-      eval_call("      ", j);
-      s << "      evql_update(A, lds, acc, bypass, r + " << j << ", o);\n";
+    if (probe_ahead()) {
+      // both rows of the step are evaluated and their identity slots read before either is
+      // consumed: one exposed LDS round trip per step instead of one per row.  A slot that
+      // row 0 claims after row 1's read is seen by row 1's compare-and-swap (evql_lds_find_from)
+      s << "      EvqlRowOut o0, o1;\n";
+      for (int j = 0; j < 2; ++j) eval_call("      ", j, nullptr, j ? "o1" : "o0");
+      for (int j = 0; j < 2; ++j) {
+        s << "      const u64 k" << j << " = evql_lds_peek(&lds[(u32) o" << j
+          << ".ident & (EVQL_LDS_SLOTS - 1)]);\n";
+      }
+      for (int j = 0; j < 2; ++j) {
+        s << "      evql_update(A, lds, acc, bypass, r + " << j << ", o" << j << ", k" << j << ");\n";
+      }
+    } else {
+      s << "      EvqlRowOut o;\n";
+      for (int j = 0; j < 2; ++j) {
+        eval_call("      ", j);
+        s << "      evql_update(A, lds, acc, bypass, r + " << j << ", o);\n";
+      }
     }
     s << "    }\n  }\n";
     });
+    window32 = true;
 
     // epilogue
     zone_skip_flush("  ");
@@ -841,11 +924,13 @@ struct Gen {
     s << "  const u32 tid = threadIdx.x;\n";
     s << "  __shared__ u32 wsum[EVQL_NWAVE];\n";
     zone_skip_decl("  ");
+    window32 = false;
     tile_loop_twice("  ", [&] {
     s << "  for (u64 t = blockIdx.x; t < A.ntiles; t += gridDim.x) {\n";
     // (the host does not clear tile_count: a skipped tile still stores its 0)
     zone_skip("    ", "if (tid == 0) tile_count[t] = 0;");
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     tile_loads("    ", &where_cols);
     s << "    u32 cnt = 0;\n";
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
@@ -864,6 +949,7 @@ struct Gen {
     s << "    __syncthreads();\n";
     s << "  }\n";
     });
+    window32 = true;
     zone_skip_flush("  ");
     s << "}\n\n";
 
@@ -880,6 +966,7 @@ struct Gen {
     s << "    const u64 dst0 = S.tile_offset[t] - S.window_base;\n";
     s << "    if (S.tile_offset[t + 1] == S.tile_offset[t]) continue;\n";
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     tile_loads("    ");
     s << "    u32 live = 0;  // bit 2u + j: row (u, j) of this lane passes\n";
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
@@ -950,6 +1037,7 @@ struct Gen {
     s << "  const u32 tid = threadIdx.x;\n";
     s << "  for (u64 t = blockIdx.x; t < A.ntiles; t += gridDim.x) {\n";
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     tile_loads("    ");
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
@@ -1036,10 +1124,12 @@ struct Gen {
     s << "  for (u32 i = tid; i < EVQL_NPART; i += EVQL_BLOCK) hist[i] = 0;\n  __syncthreads();\n";
     s << "  const u64 t0 = (u64) blockIdx.x * P.tiles_per_wg;\n";
     s << "  const u64 t1 = t0 + P.tiles_per_wg < A.ntiles ? t0 + P.tiles_per_wg : A.ntiles;\n";
+    window32 = false;
     tile_loop_twice("  ", [&] {
     s << "  for (u64 t = t0; t < t1; ++t) {\n";
     zone_skip("    ", "", false);  // (counted by the scatter pass)
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     tile_loads("    ");
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
@@ -1050,6 +1140,7 @@ struct Gen {
     }
     s << "    }\n  }\n";
     });
+    window32 = true;
     s << "  __syncthreads();\n";
     s << "  for (u32 i = tid; i < EVQL_NPART; i += EVQL_BLOCK) P.counts[(u64) i * P.nwg + blockIdx.x] = "
          "hist[i];\n";
@@ -1079,6 +1170,7 @@ struct Gen {
     s << "  for (u64 t = t0; t < t1; ++t) {\n";
     zone_skip("    ", "");
     s << "    const u64 base = (A.tile0 + t) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("    ");
     tile_loads("    ");
     // sweep 1: how many tuples of this tile go to each coarse bucket
     s << "    for (u32 i = tid; i < EVQL_NCOARSE; i += EVQL_BLOCK) hist[i] = 0;\n";

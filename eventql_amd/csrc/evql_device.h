@@ -478,15 +478,17 @@ __device__ __forceinline__ u32 evql_lds_peek32(const u32* p) {
 }
 
 // LDS table: returns the slot or -1 when no slot was found within MAXP probes
+// `cur`: the word of the identity slot keys[ident & mask] as the caller read it (evql_lds_peek),
+// possibly a while ago: a key never changes once written, and an EVQL_EMPTY that has been
+// claimed since is found out by the compare-and-swap.
 template <int MAXP>
-__device__ __forceinline__ int evql_lds_find(u64* keys, u32 mask, u64 ident, u32 h) {
+__device__ __forceinline__ int evql_lds_find_from(u64* keys, u32 mask, u64 ident, u32 h, u64 cur) {
   // Probe 0 is the identity slot (low key bits): dense small keys -- dimension
   // ids, the usual GROUP BY key -- then never collide, and in a wave the probe
   // loop runs as long as its slowest lane.  Everything else continues along the
   // mixed-hash linear chain.
   u32 s = (u32) ident & mask;
   {
-    u64 cur = evql_lds_peek(&keys[s]);
     if (cur == ident) return (int) s;
     if (cur == EVQL_EMPTY) {
       u64 old = atomicCAS(&keys[s], EVQL_EMPTY, ident);
@@ -505,6 +507,10 @@ __device__ __forceinline__ int evql_lds_find(u64* keys, u32 mask, u64 ident, u32
     s = (s + 1) & mask;
   }
   return -1;
+}
+template <int MAXP>
+__device__ __forceinline__ int evql_lds_find(u64* keys, u32 mask, u64 ident, u32 h) {
+  return evql_lds_find_from<MAXP>(keys, mask, ident, h, evql_lds_peek(&keys[(u32) ident & mask]));
 }
 
 // global (HBM) table.  Keys never change once written, so a stale plain read
