@@ -143,6 +143,7 @@ def lib():
     K.bind_chain_compact(L)
     K.bind_chain_compact_sorted(L)
     K.bind_partial_emit(L)
+    K.bind_materialize(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_create_device.argtypes = [C.c_void_p, C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_stats.argtypes = [C.c_void_p, C.POINTER(K.MergeStats)]
@@ -507,6 +508,27 @@ class Query:
         _check(lib().evql_query_emit_stats(self.h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in K.EmitStats._fields_}
 
+    materialize_stats = None  # capi.MaterializeStats fields of the last to_table()
+
+    def to_table(self, specs, sort_by=None, page_order=K.PAGE_ORDER_COLUMNS):
+        """evql_table_from_query: the groups of this executed FINAL GROUP BY as a resident
+        Table, written on the device.  specs: as for Writer, one per select expression;
+        sort_by: the name of a required unsigned-integer / datetime column among them to sort
+        the rows by (stable, ascending), or None for the order of the group records.  The query
+        is not changed; the table is independent of it and closed by the caller.
+        materialize_stats holds the call's figures."""
+        names = [c["name"] for c in specs]
+        if sort_by is not None and sort_by not in names:
+            raise EvqlError(K.EVQL_EARG, "sort column is not among the output columns: %s" % sort_by)
+        cs, _keep = LsmChain._column_specs(specs)
+        t = C.c_void_p()
+        st = K.MaterializeStats()
+        _check(lib().evql_table_from_query(self.h, cs, len(specs),
+                                           -1 if sort_by is None else names.index(sort_by),
+                                           page_order, C.byref(t), C.byref(st)))
+        self.materialize_stats = {f[0]: getattr(st, f[0]) for f in K.MaterializeStats._fields_}
+        return Table(self.table.ctx, t)
+
     def kernel_source(self):
         return lib().evql_query_kernel_source(self.h).decode()
 
@@ -733,6 +755,25 @@ def plan_partial_emit(plan, columns, n_groups, merged=False):
     _check(lib().evql_plan_partial_emit(C.byref(plan.desc), infos, len(columns), n_groups,
                                         int(merged), C.byref(d)))
     return d.value
+
+
+def plan_materialize(plan, columns, specs, sort_by=None, merged=False):
+    """evql_plan_materialize: would Query.to_table(specs, sort_by) take a result of `plan`?
+    capi.MAT_DEVICE (0) or the reason why not (capi.MAT_*; last_error() names it); no device
+    needed, columns as for compile_only.  sort_by: a column name or an index"""
+    infos = _column_infos(columns)
+    cs, _keep = LsmChain._column_specs(specs)
+    names = [c["name"] for c in specs]
+    sort = -1 if sort_by is None else (sort_by if isinstance(sort_by, int) else names.index(sort_by))
+    d = C.c_int()
+    _check(lib().evql_plan_materialize(C.byref(plan.desc), infos, len(columns), cs, len(specs),
+                                       sort, int(merged), C.byref(d)))
+    return d.value
+
+
+def last_error():
+    """evql_last_error of the calling thread"""
+    return lib().evql_last_error().decode(errors="replace")
 
 
 def compile_only(plan, columns, cache_dir=None):

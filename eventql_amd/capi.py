@@ -309,5 +309,34 @@ def bind_chain_compact_sorted(lib):
     lib.evql_lsm_chain_compact_sorted.argtypes = [
         C.c_void_p, C.POINTER(ColumnSpec), C.c_int, C.c_char_p, C.c_int, C.c_int,
         C.POINTER(C.c_void_p), C.POINTER(CompactStats), C.POINTER(CompactSortStats)]
+
+
+# *decision of evql_plan_materialize
+(MAT_DEVICE, MAT_PARTIAL_MODE, MAT_COLUMN_COUNT, MAT_NESTED_SPEC, MAT_TYPE_MISMATCH,
+ MAT_SORT_COLUMN, MAT_BARE_SCAN, MAT_ORDER_LIMIT, MAT_TOO_WIDE, MAT_POST_AGGREGATE,
+ MAT_EXACT_SUM, MAT_INT64, MAT_NIL, MAT_KEY_EXPR, MAT_FIRST_ROW, MAT_SORT_KEY,
+ MAT_SORT_ROWS) = range(17)
+
+
+class MaterializeStats(C.Structure):
+    """evql_materialize_stats_t"""
+    _fields_ = [("rows", C.c_uint64), ("string_bytes", C.c_uint64),
+                ("presorted", C.c_uint32), ("passes", C.c_uint32),
+                ("n_kernel_launches", C.c_uint32), ("n_host_waits", C.c_uint32),
+                ("gather_ms", C.c_float), ("sort_ms", C.c_float), ("encode_ms", C.c_float)]
+
+
+def bind_materialize(lib):
+    """declares evql_table_from_query and evql_plan_materialize on the loaded library"""
+    lib.evql_table_from_query.restype = C.c_int
+    lib.evql_table_from_query.argtypes = [
+        C.c_void_p, C.POINTER(ColumnSpec), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+        C.POINTER(MaterializeStats)]
+    lib.evql_plan_materialize.restype = C.c_int
+    lib.evql_plan_materialize.argtypes = [
+        C.POINTER(PlanDesc), C.POINTER(ColumnInfo), C.c_int, C.POINTER(ColumnSpec), C.c_int,
+        C.c_int, C.c_int, C.POINTER(C.c_int)]
+
+
 FLOAT_SUM_FAST = 0
 FLOAT_SUM_EXACT = 1

@@ -2340,6 +2340,110 @@ __global__ void __launch_bounds__(kBlock) k_emit_str_bytes(const EmitArgs* ap, u
   }
 }
 
+// ---- a GROUP BY result as SoA columns for the device writer (materialize.cc) ------------
+// One thread per group everywhere; lane l of a wave owns group g0 + l, so the stores to
+// values[c][g] / nulls[c][g] of one column are consecutive across the wave.
+__global__ void __launch_bounds__(kBlock) k_mat_first_rows(const u64* records, u64 n, u32 rw, u32 word,
+                                                           u64 row_limit, u64* rows, u64* status) {
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    u64 r = records[i * rw + word];
+    if (r >= row_limit) {  // (never hand an unrecorded first row to the gather)
+      status[1] = 1;
+      r = EVQL_EMPTY;
+    }
+    rows[i] = r;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mat_fixed(const MatArgs* ap, u64 n) {
+  const MatArgs& a = *ap;
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64* rec = (const u64*) a.records + i * a.rw;
+    u32 null_in_required = 0;
+    for (u32 c = 0; c < a.ncols; ++c) {
+      const MatCol& e = a.col[c];
+      u64 bits = 0;
+      bool null = false;
+      if (e.kind == 0) {
+        if (rec[0] == 2) null = true; else bits = rec[1];
+      } else if (e.kind == 1) {
+        bits = rec[e.word];
+        if (e.count_word >= 0) {
+          const u64 cnt = rec[e.count_word];
+          if (cnt == 0) {
+            bits = 0;
+            null = true;
+          } else if (e.is_mean) {
+            const double m = evql_as_f64(bits) / (double) cnt;
+            bits = evql_f64_bits(m);
+          }
+        }
+      } else {
+        const u64 raw = ((const u64*) a.first_vals)[(u64) e.src * n + i];
+        null = a.first_tags[(u64) e.src * n + i] & 1;
+        bits = e.to_float ? evql_f64_bits((double) raw) : raw;
+      }
+      if (e.nulls) {
+        e.nulls[i] = null ? 1 : 0;
+      } else if (null) {
+        null_in_required |= 1u << c;
+      }
+      if (e.is_string) continue;  // the value word: k_mat_str_bytes
+      if (null) bits = 0;
+      e.values[i] = e.is_bool ? (u64) (bits != 0) : bits;
+    }
+    if (null_in_required) atomicOr((unsigned long long*) &a.status[0], (unsigned long long) null_in_required);
+  }
+}
+
+// length of string cell i of column e, 0 for NULL and -- flagged -- for a string outside the
+// source column's byte stream; *off = where its bytes begin there
+__device__ __forceinline__ u32 mat_str_len(const MatArgs& a, const MatCol& e, u64 n, u64 i,
+                                           u64 src_bytes, u64* off) {
+  const bool null = a.first_tags[(u64) e.src * n + i] & 1;
+  const u64 sp = ((const u64*) a.first_vals)[(u64) e.src * n + i];
+  const u64 len = null ? 0ull : sp >> 40;
+  *off = sp & kStrOffMask;
+  if (len && (*off >= src_bytes || len > src_bytes - *off)) {
+    a.status[1] = 1;
+    return 0;
+  }
+  return (u32) len;
+}
+
+__global__ void __launch_bounds__(kBlock) k_mat_str_sizes(const MatArgs* ap, u32 c, u64 n, u64 src_bytes,
+                                                          u64* sizes) {
+  const MatArgs& a = *ap;
+  const MatCol& e = a.col[c];
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    u64 off;
+    sizes[i] = mat_str_len(a, e, n, i, src_bytes, &off);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mat_str_bytes(const MatArgs* ap, u32 c, u64 n, const u8* image,
+                                                          const u64* pages, u64 src_bytes,
+                                                          const u64* offsets, u8* heap, u64 heap_cap) {
+  const MatArgs& a = *ap;
+  const MatCol& e = a.col[c];
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (u64) gridDim.x * blockDim.x) {
+    u64 off;
+    u32 len = mat_str_len(a, e, n, i, src_bytes, &off);
+    const u64 dst = offsets[i];
+    if (dst > heap_cap || len > heap_cap - dst) {
+      a.status[1] = 1;
+      e.values[i] = 0;
+      continue;
+    }
+    for (u32 k = 0; k < len; ++k) heap[dst + k] = vbyte_fwd(image, pages, off + k);
+    e.values[i] = ((u64) len << 40) | dst;
+  }
+}
+
 // ---- EVQL_MODE_PARTIAL rows on the device (results.cc emit_partial_on_device) ----------
 // One thread per group everywhere; sizes and bytes come from the same two helpers, so every
 // store lies inside the group's scanned range.
@@ -3465,6 +3569,38 @@ hipError_t launch_emit_str_sizes(const EmitArgs* d_args, uint32_t c, uint64_t n,
 hipError_t launch_emit_str_bytes(const EmitArgs* d_args, uint32_t c, uint64_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_emit_str_bytes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, c, (u64) n);
+  return hipGetLastError();
+}
+
+hipError_t launch_mat_first_rows(const uint64_t* records, uint64_t n, uint32_t rw, uint32_t word,
+                                 uint64_t row_limit, uint64_t* rows, uint64_t* status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mat_first_rows, dim3(grid_for(n)), dim3(kBlock), 0, s, (const u64*) records,
+                     (u64) n, rw, word, (u64) row_limit, (u64*) rows, (u64*) status);
+  return hipGetLastError();
+}
+
+hipError_t launch_mat_fixed(const MatArgs* d_args, uint64_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mat_fixed, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, (u64) n);
+  return hipGetLastError();
+}
+
+hipError_t launch_mat_str_sizes(const MatArgs* d_args, uint32_t c, uint64_t n, uint64_t src_bytes,
+                                uint64_t* sizes, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mat_str_sizes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, c, (u64) n,
+                     (u64) src_bytes, (u64*) sizes);
+  return hipGetLastError();
+}
+
+hipError_t launch_mat_str_bytes(const MatArgs* d_args, uint32_t c, uint64_t n, const uint8_t* image,
+                                const uint64_t* pages, uint64_t src_bytes, const uint64_t* offsets,
+                                uint8_t* heap, uint64_t heap_cap, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mat_str_bytes, dim3(grid_for(n)), dim3(kBlock), 0, s, d_args, c, (u64) n,
+                     image, (const u64*) pages, (u64) src_bytes, (const u64*) offsets, heap,
+                     (u64) heap_cap);
   return hipGetLastError();
 }
 

@@ -725,6 +725,27 @@ int evql_lsm_chain_compact_sorted(evql_lsm_chain_t* ch, const evql_column_spec_t
   return compact_chain(ch, cols, ncols, row_order, page_order, out, stats, &sort);
 }
 
+int evql_table_from_query(evql_query_t* q, const evql_column_spec_t* cols, int ncols, int sort_column,
+                          int page_order, evql_table_t** out, evql_materialize_stats_t* stats) {
+  API_TRY
+  if (!q || !cols || !out || ncols <= 0) return fail(EVQL_EARG, "bad arguments");
+  if (page_order != EVQL_PAGE_ORDER_COLUMNS && page_order != EVQL_PAGE_ORDER_ROWS) {
+    return fail(EVQL_EARG, "bad page order");
+  }
+  std::vector<ColumnSpec> specs;
+  for (int i = 0; i < ncols; ++i) {
+    if (!cols[i].name) return fail(EVQL_EARG, "output column without a name");
+    specs.push_back(column_spec_of(cols[i]));
+  }
+  if (hipSetDevice(q->ctx->device) != hipSuccess) return fail(EVQL_EDEVICE, "hipSetDevice failed");
+  evql_table* t = nullptr;
+  Status st = table_from_query(q, specs, sort_column, page_order, &t, stats);
+  if (!st.ok()) return ret(st);
+  *out = t;
+  return EVQL_OK;
+  API_CATCH
+}
+
 void evql_query_destroy(evql_query_t* q) { delete q; }
 
 // a chain query runs the scans of all its tables (head first), then merges their groups
@@ -1144,6 +1165,46 @@ int evql_plan_partial_emit(const evql_plan_desc_t* plan, const evql_column_info_
   q.merged = merged != 0;
   PartialEmitPlan pplan;
   *decision = int(plan_partial_emit(partial_emit_input(&q, n_groups), &pplan));
+  return EVQL_OK;
+  API_CATCH
+}
+
+int evql_plan_materialize(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                          int ncolumns, const evql_column_spec_t* cols, int ncols, int sort_column,
+                          int merged, int* decision) {
+  API_TRY
+  if (!plan || (!columns && ncolumns) || (!cols && ncols) || ncols < 0 || !decision) {
+    return fail(EVQL_EARG, "null argument");
+  }
+  TableLayout layout;
+  layout.version = 2;
+  layout.num_rows = 0;
+  for (int i = 0; i < ncolumns; ++i) {
+    ColumnLayout c;
+    c.name = columns[i].name;
+    c.logical_type = ColumnType(columns[i].logical_type);
+    c.storage_type = ColumnEncoding(columns[i].storage_type);
+    c.column_id = columns[i].column_id;
+    c.rlevel_max = columns[i].rlevel_max;
+    c.dlevel_max = columns[i].dlevel_max;
+    layout.columns.push_back(c);
+  }
+  evql_query q;
+  q.group_mode = plan->group_mode;
+  q.float_sum_mode = plan->float_sum_mode;
+  q.float_sum_bound = plan->float_sum_bound;
+  bool unsupported = false;
+  Status st = build_kernel_plan(layout, plan, &q, &unsupported);
+  if (!st.ok()) return ret(st);
+  q.merged = merged != 0;
+  std::vector<MatSpec> specs;
+  for (int i = 0; i < ncols; ++i) {
+    specs.push_back(MatSpec{cols[i].name ? cols[i].name : "", uint32_t(cols[i].logical_type),
+                            cols[i].rlevel_max, cols[i].dlevel_max});
+  }
+  MatPlan mplan;
+  *decision = int(plan_materialize(materialize_input(&q, &specs, sort_column), &mplan));
+  set_last_error(mplan.reason);
   return EVQL_OK;
   API_CATCH
 }

@@ -358,18 +358,9 @@ Status sha1_ranges_on_device(evql_ctx* ctx, const void* bytes, size_t len, const
   return Status();
 }
 
-// the groups as dense device records [kind, slot words...] on their way to the host
-struct FetchedRecords {
-  uint32_t nwords = 0;        // slot words of a record
-  uint64_t* d_rec = nullptr;  // borrowed (small buffer, merged dense records) or `own`
-  DevBuf<uint64_t> own;       // records that do not fit the small buffer
-  uint64_t n = 0;
-  uint64_t total = 0;         // groups of the result before LIMIT
-};
-
 // step 1: the dense records of the partitioned path and the compacted slots of the group
-// table (after an exchange: of the merged table) in one buffer
-static Status collect_records(evql_query* q, FetchedRecords* r) {
+// table (after an exchange: of the merged table) in one buffer (FetchedRecords: runtime.h)
+Status collect_records(evql_query* q, FetchedRecords* r) {
   evql_ctx* ctx = q->ctx;
   const KernelPlan& kp = q->rplan();
   hipStream_t s = ctx->stream;

@@ -13,6 +13,7 @@
 #include "aot_kernels.h"
 #include "codegen.h"
 #include "cstable_format.h"
+#include "materialize_plan.h"
 #include "plan_ir.h"
 
 namespace evql {
@@ -652,6 +653,20 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
 // what plan_partial_emit (partial_emit_plan.h) decides on for a result of n groups of q
 PartialEmitInput partial_emit_input(const evql_query* q, uint64_t n);
+// the groups as dense device records [kind, slot words...] on their way to the host or to the
+// device writer (materialize.cc)
+struct FetchedRecords {
+  uint32_t nwords = 0;        // slot words of a record
+  uint64_t* d_rec = nullptr;  // borrowed (small buffer, merged dense records) or `own`
+  DevBuf<uint64_t> own;       // records that do not fit the small buffer
+  uint64_t n = 0;
+  uint64_t total = 0;         // groups of the result before LIMIT
+};
+Status collect_records(evql_query* q, FetchedRecords* r);
+// materialize.cc: evql_table_from_query
+MatInput materialize_input(const evql_query* q, const std::vector<MatSpec>* specs, int sort_column);
+Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int sort_column,
+                        int page_order, evql_table** out, evql_materialize_stats_t* stats);
 Status sha1_ranges_on_device(evql_ctx* ctx, const void* bytes, size_t len, const uint64_t* offsets,
                              size_t n, uint8_t* out20);
 

@@ -1044,6 +1044,75 @@ int evql_lsm_chain_compact_sorted(evql_lsm_chain_t* ch, const evql_column_spec_t
                                   evql_table_t** out, evql_compact_stats_t* stats /* may be NULL */,
                                   evql_compact_sort_stats_t* sort_stats /* may be NULL */);
 
+/*
+ * Result materialisation: the groups of an executed EVQL_MODE_FINAL GROUP BY written as ONE
+ * resident cstable, without leaving the device -- the inner statement of
+ * `SELECT .. FROM (SELECT .. GROUP BY ..) ..` (sql/qtree/SubqueryNode.cc) stays in HBM and the
+ * outer operator is created over *out.  The dense group records are read into SoA columns
+ * (value words + NULL bytes, string bytes gathered from the source column's pages), optionally
+ * sorted by one column with the stable radix sort of evql_lsm_chain_compact_sorted, and encoded
+ * by the device writer (evql_table_from_device_columns_ordered; `page_order` is handed to it
+ * unchanged).
+ *
+ * `q` is over one table or a chain (evql_query_create_chain) and may have been exchanged; it
+ * is not changed: evql_query_next_batch afterwards returns what it would have returned, and
+ * the call may be repeated.  cols[i] describes output column i = select expression i.  *out
+ * is independent of `q`, outlives it and is closed by the caller.  There is no minimum group
+ * count; 0 groups give a table of 0 rows.
+ *
+ * Cells: the exact group key (a bare column); bare aggregates -- count, integer sum, fast
+ * float sum, count_distinct: the state word; min / max: NULL without a non-NULL value; mean:
+ * sum / double(count), NULL at count 0 --; a bare column read from the group's first row
+ * (strings with their bytes), not out of merged records or nested scans.
+ * Types: UINT64 -> unsigned integer, TIMESTAMP64 -> datetime, FLOAT64 -> float, BOOL ->
+ * boolean, STRING -> string; the storage encoding is any the device writer takes for the
+ * logical type, a value it cannot hold is treated as evql_table_from_device_columns treats it.
+ * A column that can be NULL needs dlevel_max == 1: a NULL that meets a required column fails
+ * the call with EVQL_ERUNTIME ("NULL in required column <name>") and no table.
+ *
+ * Row order: without a sort column (-1) that of the dense records -- unspecified, as for any
+ * GROUP BY.  With one: sorted stably ascending by that column's value word; key statistics,
+ * then ceil(bit_length(max - min) / 8) digit passes, none for presorted keys.
+ *
+ *   EVQL_EARG    null arguments, a query that has not executed, EVQL_MODE_PARTIAL, ncols
+ *                different from the select count, a repeated / nested spec, a bad page_order
+ *                or sort_column, a select expression whose type does not fit the spec's
+ *   EVQL_ENOTSUP (the message names the reason) post-aggregate arithmetic, an exact float sum,
+ *                an INT64- or NIL-typed column, a computed or hashed key that is no first-row
+ *                bare column, first-row columns of a merged result or a nested scan, a bare
+ *                scan, ORDER BY / LIMIT set, more than 32 columns, a sort column that is
+ *                optional or not unsigned-integer / datetime, more than 2^32 - 1 rows with a
+ *                sort column
+ *   EVQL_ERUNTIME a NULL in a required column; a first row, string position or permutation
+ *                entry outside its array (nothing is stored for it)
+ */
+typedef struct {
+  uint64_t rows;              /* groups written */
+  uint64_t string_bytes;      /* bytes of all gathered string heaps */
+  uint32_t presorted, passes; /* as evql_compact_sort_stats_t; 0, 0 without a sort column */
+  uint32_t n_kernel_launches; /* gather + sort + permute, without the writer's */
+  uint32_t n_host_waits;      /* at most 3: heap sizes, key statistics, the writer's */
+  float gather_ms, sort_ms, encode_ms; /* device time */
+} evql_materialize_stats_t;
+
+int evql_table_from_query(evql_query_t* q, const evql_column_spec_t* cols, int ncols,
+                          int sort_column /* -1: none */, int page_order,
+                          evql_table_t** out, evql_materialize_stats_t* stats /* may be NULL */);
+
+/* The decision of evql_table_from_query without a device, as evql_plan_partial_emit gives it
+ * for PARTIAL rows; columns as for evql_compile_only.  `merged`: the groups come out of an
+ * exchange or a chain merge.  *decision: 0 = accepted, else why not -- 1 PARTIAL mode, 2 ncols
+ * is not the select count, 3 a repeated / nested spec, 4 a type mismatch, 5 a bad sort_column
+ * (these are EVQL_EARG to evql_table_from_query), 6 a bare scan, 7 ORDER BY / LIMIT (never
+ * here: a plan has none), 8 more than 32 columns, 9 post-aggregate arithmetic, 10 an exact
+ * float sum, 11 an INT64 column, 12 a NIL column, 13 a computed or hashed key / expression
+ * that is no first-row bare column, 14 a first-row column of a merged result or nested scan,
+ * 15 a sort column that is optional or not unsigned-integer / datetime, 16 too many rows to
+ * sort (never here).  The reason is left in evql_last_error(). */
+int evql_plan_materialize(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                          int ncolumns, const evql_column_spec_t* cols, int ncols,
+                          int sort_column, int merged, int* decision);
+
 /* ------------------------------------------------------------------------ */
 /* build support                                                              */
 /* ------------------------------------------------------------------------ */

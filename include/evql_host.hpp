@@ -167,6 +167,23 @@ class GpuGroupByScan : public TableExpression {
     return e;
   }
 
+  // The groups of the executed operator as a resident cstable, written on the device
+  // (evql_table_from_query): the inner statement of a SubqueryNode stays in HBM, the outer
+  // operator is created over the returned table, which the caller closes (evql_table_close).
+  // specs[i] describes select expression i; sort_column -1 = the order of the group records.
+  // Throws NotLowerable where the result keeps the SVector path (the message names the
+  // reason); the operator is unchanged either way and nextBatch still yields every row.
+  evql_table_t* toTable(const std::vector<evql_column_spec_t>& specs, int sort_column = -1,
+                        int page_order = EVQL_PAGE_ORDER_COLUMNS,
+                        evql_materialize_stats_t* stats = nullptr) {
+    evql_table_t* t = nullptr;
+    int rc = evql_table_from_query(query_, specs.data(), int(specs.size()), sort_column, page_order,
+                                   &t, stats);
+    if (rc == EVQL_ENOTSUP) throw NotLowerable(evql_last_error());
+    if (rc != EVQL_OK) throw std::runtime_error(evql_last_error());
+    return t;
+  }
+
   // Fuses LimitExpression(limit, offset, OrderByExpression(specs, this)) into the
   // operator (orderby.cc:60-160, limit.cc:52-125); limit < 0 = ORDER BY only.
   // Throws NotLowerable when the first sort key cannot be read on the device, in
