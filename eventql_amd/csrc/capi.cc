@@ -1090,6 +1090,7 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
   // bit widths are not known without pages: payload_bytes carries the width.  On a required
   // UINT64_PLAIN / UINT64_LEB128 column a width of 8 / 16 / 32 asks for the shape over the
   // flat narrow copy a resident table keeps of it (query_prepare makes the same switch).
+  bool repacked = false;
   for (auto& c : q.kp.cols) {
     const evql_column_info_t& ci = columns[c.layout_index];
     const uint32_t w = uint32_t(ci.payload_bytes);
@@ -1104,6 +1105,7 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
       c.mode = ColAccess::NARROW;
       c.bits = w;
       c.packed = true;
+      repacked = true;
     } else if (w == 32 && ci.dlevel_max == 0 && ci.rlevel_max == 0 && c.mode == ColAccess::PLAIN64 &&
                c.stype == EVQL_T_FLOAT64 && !c.from_uint_to_float &&
                ColumnEncoding(ci.storage_type) == ColumnEncoding::FLOAT_IEEE754) {
@@ -1111,8 +1113,11 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
       c.mode = ColAccess::NARROW_F32;
       c.bits = 32;
       c.packed = true;
+      repacked = true;
     }
   }
+  // (the access modes changed: the launch shape is chosen again, as query_prepare does)
+  if (repacked && !q.kp.partitioned) choose_launch_shape(&q.kp, plan->groups_hint);
   q.source = generate_kernel_source(&q.kp);
   std::vector<char> code;
   st = compile_to_code_object(q.source, &code, true);

@@ -103,6 +103,12 @@ struct KernelPlan {
   // entries of the lane-private accumulator cache in front of the LDS table (1, or 4 for
   // plans with 2 .. 4 expected groups), codegen_kernels.inc evql_update
   int lane_cache = 1;
+  // evql_scan_agg loads the next tile, raw, while it evaluates the current one (DESIGN.md 3.1,
+  // codegen_kernels.inc scan_kernel).  Chosen by choose_launch_shape where `prefetch_allowed`:
+  // false for nested scans, under EVQL_SCAN_PREFETCH=0 (build_kernel_plan), and once the
+  // prefetching kernel of the plan has compiled with scratch memory (compile_plan_kernels).
+  bool prefetch = false;
+  bool prefetch_allowed = false;
   // high cardinality: radix-partition the passing rows into 2^part_bits buckets
   // of tuples, then aggregate each bucket in LDS (codegen_kernels.inc)
   bool partitioned = false;

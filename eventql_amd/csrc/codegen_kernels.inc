@@ -449,8 +449,9 @@ struct Gen {
     s << ind << "const u32 wlen = whi > wlo ? whi - wlo : 0u;\n";
     s << ind << "const u32 wrel = 2u * tid - wlo;\n";
   }
+  // (step_local: the row's values are x<i>s[j], decoded in the step from a raw tile, no tags)
   void eval_call(const char* ind, int j, const std::vector<bool>* only = nullptr,
-                 const char* out = "o") {
+                 const char* out = "o", bool step_local = false) {
     if (window32) {
       s << ind << "evql_eval_row(A, r + " << j << ", wrel + (u32) (u * EVQL_BLOCK * 2 + " << j
         << ") < wlen";
@@ -463,16 +464,160 @@ struct Gen {
         s << ", 0ull, 0u";
         continue;
       }
+      if (step_local) {
+        s << ", x" << i << "s[" << j << "], 0u";
+        continue;
+      }
       s << ", x" << i << "[u][" << j << "], y" << i << "[u][" << j << "]";
     }
     s << ", " << out << ");\n";
   }
 
+  // ---- the prefetching tile loop of evql_scan_agg (KernelPlan::prefetch) ------------------
+  // Two tiles are held RAW, as the words the loads returned: N, the tile being loaded, and C,
+  // the tile being evaluated.  One body: load N = next tile -> evaluate C -> C = N.  The loads
+  // of a tile then have a whole tile's evaluation to arrive in, where the plain loop waits for
+  // them with nothing else to issue.  All columns are flat narrow / float32 copies without
+  // tags (choose_launch_shape): one word per step and column for 8 / 16 bits, two for 32.
+  static int raw_words(const ColAccess& c) { return c.bits == 32 ? 2 : 1; }
+  void raw_tile_decls(const char* ind, const char* name, bool zero) {
+    for (int i = 0; i < NC; ++i) {
+      s << ind << "u32 " << name << i << "[EVQL_UNROLL][" << raw_words(kp.cols[i]) << "]"
+        << (zero ? " = {}" : "") << ";\n";
+    }
+  }
+  void raw_tile_loads(const char* ind) {
+    s << "#pragma unroll\n" << ind << "for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
+    s << ind << "  const u64 r = lbase + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
+    for (int i = 0; i < NC; ++i) {
+      const ColAccess& c = kp.cols[i];
+      const int hi = raw_words(c) - 1;
+      // (the accessors' names of tile_loads; their u32 overloads return the words as loaded:
+      // evql_f32_ld, evql_narrow_ld)
+      if (c.mode == ColAccess::NARROW_F32) {
+        s << ind << "  evql_f32_x2(A.col[" << i << "].base, r, n" << i << "[u][0], n" << i << "[u][" << hi
+          << "]);\n";
+      } else {
+        s << ind << "  evql_bitpacked_x2<" << c.bits << ">(A.col[" << i << "].base, r, n" << i << "[u][0], n"
+          << i << "[u][" << hi << "]);\n";
+      }
+    }
+    s << ind << "}\n";
+  }
+  // the head of a step: its raw words are touched, for every row, then decoded into x<i>s[2]
+  void raw_step_decode(const char* ind) {
+    s << ind << "asm(\"\" : ";
+    bool first = true;
+    for (int i = 0; i < NC; ++i) {
+      for (int w = 0; w < raw_words(kp.cols[i]); ++w) {
+        s << (first ? "" : ", ") << "\"+v\"(c" << i << "[u][" << w << "])";
+        first = false;
+      }
+    }
+    s << ");\n";
+    for (int i = 0; i < NC; ++i) {
+      const ColAccess& c = kp.cols[i];
+      const int hi = raw_words(c) - 1;
+      s << ind << "u64 x" << i << "s[2]; ";
+      if (c.mode == ColAccess::NARROW_F32) {
+        s << "evql_f32_dec(c" << i << "[u][0], c" << i << "[u][" << hi << "], x" << i << "s[0], x" << i
+          << "s[1]);\n";
+      } else {
+        s << "evql_narrow_dec<" << c.bits << ">(c" << i << "[u][0], c" << i << "[u][" << hi << "], x" << i
+          << "s[0], x" << i << "s[1]);\n";
+      }
+    }
+  }
+  void raw_tile_copy(const char* ind) {
+    s << "#pragma unroll\n" << ind << "for (int u = 0; u < EVQL_UNROLL; ++u) {\n" << ind << " ";
+    for (int i = 0; i < NC; ++i) {
+      for (int w = 0; w < raw_words(kp.cols[i]); ++w) {
+        s << " c" << i << "[u][" << w << "] = n" << i << "[u][" << w << "];";
+      }
+    }
+    s << "\n" << ind << "}\n";
+  }
+
   // ---- the fused scan kernel --------------------------------------------------------
   // (the tile loop reads the identity slots of a step's two rows ahead of their updates)
   bool probe_ahead() const { return grouped && S > 0 && !kp.has_ident2(); }
+  // rows (u, 0) and (u, 1) of a tile: evaluate, update
+  void scan_step(const std::string& ind, bool step_local) {
+    const char* in = ind.c_str();
+    if (probe_ahead()) {
+      // both rows of the step are evaluated and their identity slots read before either is
+      // consumed: one exposed LDS round trip per step instead of one per row.  A slot that
+      // row 0 claims after row 1's read is seen by row 1's compare-and-swap (evql_lds_find_from)
+      s << in << "EvqlRowOut o0, o1;\n";
+      for (int j = 0; j < 2; ++j) eval_call(in, j, nullptr, j ? "o1" : "o0", step_local);
+      for (int j = 0; j < 2; ++j) {
+        s << in << "const u64 k" << j << " = evql_lds_peek(&lds[(u32) o" << j
+          << ".ident & (EVQL_LDS_SLOTS - 1)]);\n";
+      }
+      for (int j = 0; j < 2; ++j) {
+        s << in << "evql_update(A, lds, acc, bypass, r + " << j << ", o" << j << ", k" << j << ");\n";
+      }
+    } else {
+      s << in << "EvqlRowOut o;\n";
+      for (int j = 0; j < 2; ++j) {
+        eval_call(in, j, nullptr, "o", step_local);
+        s << in << "evql_update(A, lds, acc, bypass, r + " << j << ", o);\n";
+      }
+    }
+  }
+  // The prefetching form of the tile loop without zone test (grouped, LDS table).  `tc` is the
+  // tile held in C, `have` whether there is one.  Past a workgroup's last tile the load is
+  // clamped to the tile it holds -- a tile of this launch, whatever lies behind the arrays --
+  // and its values are dropped.  The poll of TABLE_FULL is issued AHEAD of the cluster and
+  // tested behind the copy, where the loads are waited for anyway: every global load counts on
+  // the same in-order vmcnt, and a value tested between the cluster and the copy would wait
+  // for the whole prefetch.  (A launch that ends this way is void: the host grows the table
+  // and runs it again, so the one more tile it evaluates does not matter.)  The scheduling
+  // barriers keep the cluster in front of the evaluation and the copy behind it.
+  void prefetch_tile_loop() {
+    s << "  u32 tile_no = 0;  // tiles evaluated\n";
+    raw_tile_decls("  ", "c", false);
+    s << "  bool have = false;\n  u64 tc = 0;\n";
+    s << "  for (u64 t = blockIdx.x; have || t < A.ntiles; t += gridDim.x) {\n";
+    s << "    const bool more = t < A.ntiles;\n";
+    s << "    const u64 tl = more ? t : tc;\n";
+    s << "    u32 st = 0;\n";
+    s << "    if ((tile_no & 15u) == 0) st = __hip_atomic_load(&A.status[0], __ATOMIC_RELAXED, "
+         "__HIP_MEMORY_SCOPE_AGENT);\n";
+    s << "    const u64 lbase = (A.tile0 + tl) * (u64) EVQL_TILE_ROWS;\n";
+    raw_tile_decls("    ", "n", false);
+    raw_tile_loads("    ");
+    s << "    __builtin_amdgcn_sched_barrier(0);\n";
+    s << "    if (have) {\n";
+    s << "      const bool bypass = evql_lds_peek32(reinterpret_cast<const u32*>(&lds[EVQL_WORDS * "
+         "EVQL_LSTRIDE])) >= 4u * EVQL_BLOCK;\n";
+    s << "      const u64 base = (A.tile0 + tc) * (u64) EVQL_TILE_ROWS;\n";
+    tile_window("      ");
+    s << "#pragma unroll\n      for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
+    s << "        const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
+    raw_step_decode("        ");
+    scan_step("        ", true);
+    s << "      }\n      ++tile_no;\n    }\n";
+    s << "    __builtin_amdgcn_sched_barrier(0);\n";
+    raw_tile_copy("    ");
+    // (the volatile statement stays where it is written: the copy and its waits are not
+    // sunk behind the test of the poll, and the polled word stays in its VGPR until here)
+    s << "    asm volatile(\"\" : \"+v\"(st)";
+    for (int i = 0; i < NC; ++i) {
+      for (int w = 0; w < raw_words(kp.cols[i]); ++w) s << ", \"+v\"(c" << i << "[EVQL_UNROLL - 1][" << w << "])";
+    }
+    s << ");\n";
+    s << "    tc = tl;\n    have = more;\n";
+    s << "    if (__builtin_amdgcn_readfirstlane(st) & EVQL_ST_TABLE_FULL) break;\n";
+    s << "  }\n";
+  }
   void scan_kernel() {
-    s << "struct EvqlAcc {\n  u64 passed;\n  u64 spilled;\n";
+    // (passed / spilled: rows of this lane.  A plan with the prefetching loop counts them in 32
+    // bits, widened at the wave reduction -- one v_addc per row instead of a select and a 64-bit
+    // add; a lane sees 8 rows of a tile, 2^32 of them are beyond any table.  The other plans
+    // keep their text.)
+    const char* ctr = kp.prefetch ? "u32" : "u64";
+    s << "struct EvqlAcc {\n  " << ctr << " passed;\n  " << ctr << " spilled;\n";
     if (!grouped) s << "  u64 w[" << (NW > 0 ? NW : 1) << "];\n";
     // (the one global group's first passing row, for select expressions over its values:
     // `select s, count(1) from t`)
@@ -726,6 +871,10 @@ struct Gen {
     zone_skip_decl("  ");
     window32 = grouped;
     tile_loop_twice("  ", [&] {
+    if (kp.prefetch && !zone_test && grouped && S > 0) {
+      prefetch_tile_loop();
+      return;
+    }
     s << "  u32 tile_no = 0;\n";
     s << "  for (u64 t = blockIdx.x; t < A.ntiles; t += gridDim.x, ++tile_no) {\n";
     zone_skip("    ", "");
@@ -750,49 +899,36 @@ struct Gen {
     // the tile border.  These are shares of WAVE cycles, summed over the four waves that
     // share a SIMD here (one 1024-thread workgroup per CU): a SIMD's VALU issue is busy four
     // times that share of its time -- 71 % for today's config 3 at 18 %, DESIGN.md 6m -- so
-    // the instructions per row behind the loads do count.  Refilling a step's registers
-    // with the next tile's rows right after
-    // the step is evaluated (a ring over the unroll steps) was tried and ran 1.2-2.7x
-    // SLOWER, conditional or not: across the back edge of the tile loop the compiler's
-    // waitcnt insertion no longer knows how many loads are outstanding and emits
-    // s_waitcnt vmcnt(0) / vmcnt(1) in front of every step (the ISA shows 76 + 8 of them
-    // against vmcnt(14), (13), ... in this form), i.e. it serialises the loads.  One
-    // burst per tile stays.  A ring with hand-placed waits around inline-asm loads (and
-    // scalar page-table loads) was built as well: config 3 over 16-bit pages 0.360 ->
-    // 0.327 ms, but 10-bit config 2 1.87 -> 3.02 ms and plain config 2 2.42 -> 2.68 ms --
-    // dropped.)
+    // the instructions per row behind the loads do count.
+    // Overlapping a tile's loads with the tile in front of them, by form:
+    //  - a RING over the unroll steps (a step's registers refilled with the next tile's rows
+    //    right after the step is evaluated) ran 1.2-2.7x SLOWER, conditional or not: with
+    //    loads spread over the body, the compiler's waitcnt insertion no longer knows across
+    //    the back edge how many are outstanding and emits s_waitcnt vmcnt(0) / vmcnt(1) in
+    //    front of every step (76 + 8 of them against vmcnt(14), (13), ... here), i.e. it
+    //    serialises the loads.  A ring with hand-placed waits around inline-asm loads (and
+    //    scalar page-table loads): config 3 over 16-bit pages 0.360 -> 0.327 ms, but 10-bit
+    //    config 2 1.87 -> 3.02 ms and plain config 2 2.42 -> 2.68 ms -- dropped.
+    //  - the ROTATING form (prefetch_tile_loop: one cluster for the NEXT tile at the head of
+    //    the body, the tile held raw from the iteration before evaluated behind it, one copy
+    //    at the end) compiles as written: no vmcnt wait between the cluster and the copy but
+    //    in the cold HBM blocks, one vmcnt(0) at the copy.  It needs the tile raw (two tiles
+    //    in the registers of one decoded tile), so it serves the plans whose columns are all
+    //    narrow / float32 copies (choose_launch_shape); the others keep this loop, one burst
+    //    per tile.  DESIGN.md 6o has the measurement.
     tile_loads("    ");
     s << "#pragma unroll\n    for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << "      const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
-    if (probe_ahead()) {
-      // both rows of the step are evaluated and their identity slots read before either is
-      // consumed: one exposed LDS round trip per step instead of one per row.  A slot that
-      // row 0 claims after row 1's read is seen by row 1's compare-and-swap (evql_lds_find_from)
-      s << "      EvqlRowOut o0, o1;\n";
-      for (int j = 0; j < 2; ++j) eval_call("      ", j, nullptr, j ? "o1" : "o0");
-      for (int j = 0; j < 2; ++j) {
-        s << "      const u64 k" << j << " = evql_lds_peek(&lds[(u32) o" << j
-          << ".ident & (EVQL_LDS_SLOTS - 1)]);\n";
-      }
-      for (int j = 0; j < 2; ++j) {
-        s << "      evql_update(A, lds, acc, bypass, r + " << j << ", o" << j << ", k" << j << ");\n";
-      }
-    } else {
-      s << "      EvqlRowOut o;\n";
-      for (int j = 0; j < 2; ++j) {
-        eval_call("      ", j);
-        s << "      evql_update(A, lds, acc, bypass, r + " << j << ", o);\n";
-      }
-    }
+    scan_step("      ", false);
     s << "    }\n  }\n";
     });
     window32 = true;
 
     // epilogue
     zone_skip_flush("  ");
-    s << "  {\n    const u64 p = evql_wave_reduce<EVQL_OP_ADD_U64>(acc.passed);\n";
+    s << "  {\n    const u64 p = evql_wave_reduce<EVQL_OP_ADD_U64>(" << (kp.prefetch ? "(u64) " : "") << "acc.passed);\n";
     s << "    if ((tid & 63u) == 0 && p) atomicAdd(&A.counters[0], p);\n";
-    s << "    const u64 sp = evql_wave_reduce<EVQL_OP_ADD_U64>(acc.spilled);\n";
+    s << "    const u64 sp = evql_wave_reduce<EVQL_OP_ADD_U64>(" << (kp.prefetch ? "(u64) " : "") << "acc.spilled);\n";
     s << "    if ((tid & 63u) == 0 && sp) atomicAdd(&A.counters[1], sp);\n  }\n";
     if (!grouped) {
       // block reduction of the register accumulators, one atomic per word per block

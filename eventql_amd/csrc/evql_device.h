@@ -285,26 +285,49 @@ __device__ __forceinline__ u32 evql_bitpacked_rt(const u8* image, const u64* pag
 // tile.  Rows r, r + 1 (r even) are one non-temporal load of 2 * B / 8 bytes at its natural
 // alignment: no page table, no header, every byte requested once.  The results stay
 // evql_opaque: the `% 13` narrowing above applies to any value of known range.
+//
+// Load and decode are two halves.  evql_narrow_ld returns the words as loaded -- one dword for
+// 8 and 16 bits (w1 is not written), two for 32 -- and evql_narrow_dec makes the two values of
+// them: the prefetching tile loop of evql_scan_agg holds its next tile raw, half the registers
+// of the decoded form.  evql_narrow_x2 is decode(load), for every other caller.
 template <int B>
-__device__ __forceinline__ void evql_narrow_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+__device__ __forceinline__ void evql_narrow_ld(const u8* base, u64 r, u32& w0, u32& w1) {
   static_assert(B == 8 || B == 16 || B == 32, "narrow copies are 8, 16 or 32 bits wide");
-  u32 a, b;
   if (B == 32) {
     typedef u32 evql_u32x2n __attribute__((ext_vector_type(2)));
     const evql_u32x2n q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2n*>(base + (r << 2)));
-    a = q.x;
-    b = q.y;
+    w0 = q.x;
+    w1 = q.y;
   } else if (B == 16) {
-    const u32 q = __builtin_nontemporal_load(reinterpret_cast<const u32*>(base + (r << 1)));
-    a = q & 0xffffu;
-    b = q >> 16;
+    w0 = __builtin_nontemporal_load(reinterpret_cast<const u32*>(base + (r << 1)));
   } else {
-    const u32 q = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(base + r));
-    a = q & 0xffu;
-    b = q >> 8;
+    w0 = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(base + r));
+  }
+}
+
+template <int B>
+__device__ __forceinline__ void evql_narrow_dec(u32 w0, u32 w1, u64& v0, u64& v1) {
+  static_assert(B == 8 || B == 16 || B == 32, "narrow copies are 8, 16 or 32 bits wide");
+  u32 a, b;
+  if (B == 32) {
+    a = w0;
+    b = w1;
+  } else if (B == 16) {
+    a = w0 & 0xffffu;
+    b = w0 >> 16;
+  } else {
+    a = w0 & 0xffu;
+    b = w0 >> 8;
   }
   v0 = evql_opaque(a);
   v1 = evql_opaque(b);
+}
+
+template <int B>
+__device__ __forceinline__ void evql_narrow_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+  u32 w0, w1 = 0;
+  evql_narrow_ld<B>(base, r, w0, w1);
+  evql_narrow_dec<B>(w0, w1, v0, v1);
 }
 
 // The float32 copy the runtime keeps of a FLOAT64 column whose every value is exactly a zero,
@@ -316,13 +339,27 @@ __device__ __forceinline__ void evql_narrow_x2(const u8* base, u64 r, u64& v0, u
 // the branch of the rows that pass WHERE, a load whose rows all fail is then never waited
 // for, and the next tile's address arithmetic needs an s_waitcnt vmcnt in the middle of its
 // loads before it may reuse that load's registers (seen in config 3's evql_scan_agg).
-__device__ __forceinline__ void evql_f32_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+// The two halves (see evql_narrow_ld): evql_f32_ld returns the two float32 words as loaded,
+// evql_f32_dec widens them.  The decode carries no pin: the prefetching tile loop touches the
+// raw words at the head of each step instead, where they are all it holds of the tile.
+__device__ __forceinline__ void evql_f32_ld(const u8* base, u64 r, u32& w0, u32& w1) {
   typedef u32 evql_u32x2n __attribute__((ext_vector_type(2)));
   const evql_u32x2n q = __builtin_nontemporal_load(reinterpret_cast<const evql_u32x2n*>(base + (r << 2)));
-  double d0 = (double) __uint_as_float(q.x), d1 = (double) __uint_as_float(q.y);
-  asm("" : "+v"(d0), "+v"(d1));
+  w0 = q.x;
+  w1 = q.y;
+}
+
+__device__ __forceinline__ void evql_f32_dec(u32 w0, u32 w1, u64& v0, u64& v1) {
+  const double d0 = (double) __uint_as_float(w0), d1 = (double) __uint_as_float(w1);
   v0 = (u64) __double_as_longlong(d0);
   v1 = (u64) __double_as_longlong(d1);
+}
+
+__device__ __forceinline__ void evql_f32_x2(const u8* base, u64 r, u64& v0, u64& v1) {
+  u32 w0, w1;
+  evql_f32_ld(base, r, w0, w1);
+  evql_f32_dec(w0, w1, v0, v1);
+  asm("" : "+v"(v0), "+v"(v1));
 }
 
 // What the generated text calls: it names a column's accessor by its width whether the bits
@@ -330,6 +367,15 @@ __device__ __forceinline__ void evql_f32_x2(const u8* base, u64 r, u64& v0, u64&
 template <int B>
 __device__ __forceinline__ void evql_bitpacked_x2(const u8* flat, u64 i, u64& a, u64& b) {
   evql_narrow_x2<B>(flat, i, a, b);
+}
+// ... and whether it takes the two values (u64) or, in the prefetching tile loop, the words as
+// loaded (u32: evql_narrow_ld / evql_f32_ld), decoded later by evql_narrow_dec / evql_f32_dec.
+template <int B>
+__device__ __forceinline__ void evql_bitpacked_x2(const u8* flat, u64 i, u32& w0, u32& w1) {
+  evql_narrow_ld<B>(flat, i, w0, w1);
+}
+__device__ __forceinline__ void evql_f32_x2(const u8* base, u64 r, u32& w0, u32& w1) {
+  evql_f32_ld(base, r, w0, w1);
 }
 
 // value i of a narrow copy of runtime width (decode / gather kernels)

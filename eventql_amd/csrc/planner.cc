@@ -313,6 +313,7 @@ void choose_launch_shape(KernelPlan* kpp, uint64_t hint) {
   kp.block = 256;
   kp.partitioned = false;
   kp.lane_cache = 1;
+  kp.prefetch = false;
   // loads in flight per lane = columns x unroll; ~16 saturate HBM (measured: 2
   // columns 2.54 ms at unroll 4, 2.43 ms at unroll 8; 4 columns spill at 8)
   kp.unroll = kp.cols.size() <= 2 ? 8 : 4;
@@ -376,6 +377,20 @@ void choose_launch_shape(KernelPlan* kpp, uint64_t hint) {
     // groups against 0.50 ms for 9 and 0.56 ms for 1000).  Four lane-private accumulators
     // then hold every group a lane meets (codegen_kernels.inc evql_update).
     kp.lane_cache = (hint >= 2 && hint <= 4) ? 4 : 1;
+    // The prefetching tile loop (codegen_kernels.inc scan_kernel): the next tile is loaded raw
+    // while this one is evaluated.  Two raw tiles fit the registers only where a loaded word
+    // holds two rows or a row's value is one word: every column read through a flat narrow or
+    // float32 copy, no tag arrays.  The unroll-4 shapes of 3 and more columns (config 3 over
+    // its copies); config 2's unroll-8 shape keeps the plain loop.  Every other global load of
+    // the loop would wait for the whole prefetch with its own value (they share one in-order
+    // counter): plans with a row filter or a pair set keep the plain loop as well.
+    bool raw = kp.prefetch_allowed && kp.key_mode == KEY_EXACT && !kp.bare_scan &&
+               kp.unroll == 4 && kp.cols.size() >= 3 && !kp.has_row_filter && kp.n_distinct == 0;
+    for (const auto& c : kp.cols) {
+      raw = raw && (c.mode == ColAccess::NARROW || c.mode == ColAccess::NARROW_F32) && c.packed &&
+            !c.has_tags && (c.bits == 8 || c.bits == 16 || c.bits == 32);
+    }
+    kp.prefetch = raw;
     // (measured, round 2: a 2048-slot table runs dense keys as fast as 4096 slots, but the
     //  freed LDS does not buy a second workgroup per CU: at 64 VGPRs per wave the kernel
     //  spills -- config 3 over 16-bit pages 0.38 -> 1.03 ms; with unroll 2 on top 0.50 ms,
@@ -890,6 +905,11 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
   if (!nested && kp.where && !(zm && strcmp(zm, "0") == 0) && !expr_prints_zero_check(kp.where)) {
     collect_zone_conjuncts(kp.where, layout, kp.cols, &kp.zone_conjuncts);
   }
+
+  // The prefetching tile loop of evql_scan_agg, flat scans only.  EVQL_SCAN_PREFETCH=0 keeps
+  // the loop that waits for a tile's loads before it evaluates the tile.
+  const char* pf = getenv("EVQL_SCAN_PREFETCH");
+  kp.prefetch_allowed = !nested && !(pf && strcmp(pf, "0") == 0);
 
   choose_launch_shape(&kp, plan->groups_hint);
   return Status();

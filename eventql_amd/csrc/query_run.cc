@@ -129,6 +129,20 @@ static Status compile_plan_kernels(evql_query* q) {
   q->source = generate_kernel_source(&q->kp);
   Status st = compile_kernel(ctx, q->source, &q->module, true);
   if (!st.ok()) return st;
+  if (q->kp.prefetch) {
+    // The prefetching tile loop holds two raw tiles.  Where that does not fit the registers,
+    // the plan keeps the plain loop at its unroll (and keeps it when it is re-shaped) rather
+    // than prefetching half a tile.
+    int sc = 0;
+    if (q->module.fn &&
+        hipFuncGetAttribute(&sc, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, q->module.fn) == hipSuccess && sc != 0) {
+      q->kp.prefetch = false;
+      q->kp.prefetch_allowed = false;
+      q->source = generate_kernel_source(&q->kp);
+      st = compile_kernel(ctx, q->source, &q->module, true);
+      if (!st.ok()) return st;
+    }
+  }
   // A plan with many columns / state words can outgrow the 128 VGPRs a 1024-thread
   // workgroup leaves each wave: the scan kernel then keeps part of a tile in scratch
   // memory.  Fewer unroll steps per tile (fewer loads in flight, no scratch) are tried
