@@ -144,6 +144,7 @@ def lib():
     K.bind_chain_compact_sorted(L)
     K.bind_partial_emit(L)
     K.bind_materialize(L)
+    K.bind_order_sort(L)
     L.evql_merge_create.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_create_device.argtypes = [C.c_void_p, C.POINTER(K.PlanDesc), C.POINTER(C.c_void_p)]
     L.evql_merge_stats.argtypes = [C.c_void_p, C.POINTER(K.MergeStats)]
@@ -508,6 +509,12 @@ class Query:
         _check(lib().evql_query_emit_stats(self.h, C.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in K.EmitStats._fields_}
 
+    def order_stats(self):
+        """evql_query_order_stats: how the last fetched result was ordered (ORDER BY .. LIMIT)"""
+        s = K.OrderStats()
+        _check(lib().evql_query_order_stats(self.h, C.byref(s)))
+        return {f[0]: getattr(s, f[0]) for f in K.OrderStats._fields_}
+
     materialize_stats = None  # capi.MaterializeStats fields of the last to_table()
 
     def to_table(self, specs, sort_by=None, page_order=K.PAGE_ORDER_COLUMNS):
@@ -754,6 +761,18 @@ def plan_partial_emit(plan, columns, n_groups, merged=False):
     d = C.c_int()
     _check(lib().evql_plan_partial_emit(C.byref(plan.desc), infos, len(columns), n_groups,
                                         int(merged), C.byref(d)))
+    return d.value
+
+
+def plan_order_sort(plan, columns, order, n_records):
+    """evql_plan_order_sort: would n_records records of `plan` under `order`
+    (eventql_amd.plan.Order, or None) be sorted on the device?  capi.OSORT_DEVICE (0) or the
+    reason why not; no device needed, columns as for compile_only"""
+    infos = _column_infos(columns)
+    d = C.c_int()
+    specs, n = (order.specs, order.n) if order is not None else (None, 0)
+    _check(lib().evql_plan_order_sort(C.byref(plan.desc), infos, len(columns), specs, n,
+                                      n_records, C.byref(d)))
     return d.value
 
 

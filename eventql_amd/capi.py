@@ -227,6 +227,36 @@ def bind_partial_emit(lib):
                                            C.c_uint64, C.c_int, C.POINTER(C.c_int)]
 
 
+class OrderStats(C.Structure):
+    """evql_order_stats_t"""
+    _fields_ = [
+        ("sorted_on_device", C.c_uint32),
+        ("decision", C.c_uint32),
+        ("records", C.c_uint64),
+        ("rows", C.c_uint64),
+        ("n_keys", C.c_uint32),
+        ("n_sort_passes", C.c_uint32),
+        ("n_passes_skipped", C.c_uint32),
+        ("n_kernel_launches", C.c_uint32),
+        ("n_host_waits", C.c_uint32),
+        ("sort_ms", C.c_double),
+    ]
+
+
+# *decision of evql_plan_order_sort / OrderStats.decision
+OSORT_DEVICE, OSORT_NO_ORDER, OSORT_FEW_RECORDS, OSORT_SWITCHED_OFF, OSORT_EXPRESSION = range(5)
+OSORT_UNREADABLE, OSORT_TOO_MANY_SPECS, OSORT_TOO_MANY_RECORDS, OSORT_NAN_KEY = range(5, 9)
+ORDER_SORT_MAX_SPECS = 8
+
+
+def bind_order_sort(lib):
+    """declares evql_query_order_stats and evql_plan_order_sort"""
+    lib.evql_query_order_stats.argtypes = [C.c_void_p, C.POINTER(OrderStats)]
+    lib.evql_plan_order_sort.argtypes = [C.POINTER(PlanDesc), C.POINTER(ColumnInfo), C.c_int,
+                                         C.POINTER(SortSpec), C.c_uint32, C.c_uint64,
+                                         C.POINTER(C.c_int)]
+
+
 class KernelCacheStats(C.Structure):
     _fields_ = [
         ("memory_hits", C.c_uint64),

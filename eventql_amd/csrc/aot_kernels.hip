@@ -1574,32 +1574,85 @@ __global__ void k_copy_strings(const u8* image, const u64* pages, const u64* str
 }
 
 // ---- ORDER BY .. LIMIT ----------------------------------------------------------------
+// the order-preserving key of one record; *nan: the float value is a NaN (cmp_float64 has no
+// order for it)
+__device__ __forceinline__ u64 order_key(const OrderKeyArgs& a, const u64* rec, bool* nan) {
+  u64 v = rec[a.word];
+  if (a.from_ident) {
+    // kind 2 = NULL key: payload 0 (the comparators ignore tags)
+    if (rec[0] == 2) v = 0;
+  } else if (a.count_word >= 0) {
+    const u64 cnt = rec[a.count_word];
+    if (cnt == 0) {
+      v = 0;
+    } else if (a.is_mean) {
+      v = evql_f64_bits(evql_as_f64(v) / (double) cnt);
+    }
+  }
+  u64 key;
+  *nan = false;
+  if (a.type == 0) {
+    key = v;
+  } else if (a.type == 1) {
+    key = v ^ 0x8000000000000000ull;
+  } else {
+    *nan = (v << 1) > 0xFFE0000000000000ull;
+    if ((v << 1) == 0) v = 0;  // -0.0 == +0.0 for cmp_float64
+    key = (v >> 63) ? ~v : (v | 0x8000000000000000ull);
+  }
+  return a.descending ? ~key : key;
+}
+
 __global__ void __launch_bounds__(kBlock) k_order_keys(OrderKeyArgs a) {
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < a.n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.record_words;
-    u64 v = rec[a.word];
-    if (a.from_ident) {
-      // kind 2 = NULL key: payload 0 (the comparators ignore tags)
-      if (rec[0] == 2) v = 0;
-    } else if (a.count_word >= 0) {
-      const u64 cnt = rec[a.count_word];
-      if (cnt == 0) {
-        v = 0;
-      } else if (a.is_mean) {
-        v = evql_f64_bits(evql_as_f64(v) / (double) cnt);
+    bool nan;
+    a.keys[i] = order_key(a, (const u64*) a.records + i * a.record_words, &nan);
+  }
+}
+
+// ---- ORDER BY over a large result: the multi-key sort (results.cc sort_on_device) --------
+// keys[i] = the key of records[perm[i]]: a sort spec (plain_word 0) or the unsigned record
+// word key.word (plain_word 1: the kind word, the base word)
+__global__ void __launch_bounds__(kBlock) k_ord_key_perm(OrdKeyPermArgs a) {
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < a.key.n;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64 r = a.perm ? (u64) a.perm[i] : i;
+    u64 key = 0;
+    if (r >= a.key.n) {
+      atomicOr((unsigned long long*) a.status, (unsigned long long) kOrdStatusBounds);
+    } else {
+      const u64* rec = (const u64*) a.key.records + r * a.key.record_words;
+      if (a.plain_word) {
+        key = rec[a.key.word];
+      } else {
+        bool nan;
+        key = order_key(a.key, rec, &nan);
+        if (nan) atomicOr((unsigned long long*) a.status, (unsigned long long) kOrdStatusNaN);
       }
     }
-    u64 key;
-    if (a.type == 0) {
-      key = v;
-    } else if (a.type == 1) {
-      key = v ^ 0x8000000000000000ull;
+    a.key.keys[i] = key;
+  }
+}
+
+// out[i] = records[perm[lo + i]] for i < m: the OFFSET / LIMIT slice in sorted order
+__global__ void __launch_bounds__(kBlock) k_ord_gather(const u64* records, u32 rw, u64 n,
+                                                       const u32* perm, u64 lo, u64 m, u64* out,
+                                                       u64* status) {
+  const u64 total = m * rw;
+  for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (u64) gridDim.x * blockDim.x) {
+    const u64 row = i / rw, w = i - row * rw;
+    const u64 at = lo + row;
+    u64 r = at;
+    if (at < n && perm) r = perm[at];
+    u64 v = 0;
+    if (at >= n || r >= n) {
+      atomicOr((unsigned long long*) status, (unsigned long long) kOrdStatusBounds);
     } else {
-      if ((v << 1) == 0) v = 0;  // -0.0 == +0.0 for cmp_float64
-      key = (v >> 63) ? ~v : (v | 0x8000000000000000ull);
+      v = records[r * rw + w];
     }
-    a.keys[i] = a.descending ? ~key : key;
+    out[i] = v;
   }
 }
 
@@ -3499,6 +3552,22 @@ hipError_t launch_gather_records(const uint64_t* records, uint32_t record_words,
   if (m == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gather_records, dim3(grid_for(m * record_words)), dim3(kBlock), 0, s,
                      (const u64*) records, record_words, (const u64*) idx, (u64) m, (u64*) out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ord_key_perm(const OrdKeyPermArgs& a, hipStream_t s) {
+  if (a.key.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ord_key_perm, dim3(grid_for(a.key.n)), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ord_gather(const uint64_t* records, uint32_t record_words, uint64_t n,
+                             const uint32_t* perm, uint64_t lo, uint64_t m, uint64_t* out,
+                             uint64_t* status, hipStream_t s) {
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ord_gather, dim3(grid_for(m * record_words)), dim3(kBlock), 0, s,
+                     (const u64*) records, record_words, (u64) n, (const u32*) perm, (u64) lo,
+                     (u64) m, (u64*) out, (u64*) status);
   return hipGetLastError();
 }
 

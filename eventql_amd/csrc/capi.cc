@@ -602,6 +602,10 @@ static int create_one(evql_ctx_t* ctx, evql_table_t* table, const evql_plan_desc
   if (const char* pe = getenv("EVQL_PARTIAL_DEVICE_EMIT")) {
     if (strcmp(pe, "0") == 0) q->partial_device_emit = false;
   }
+  // EVQL_ORDER_DEVICE_SORT=0: ORDER BY over a large result keeps the host's sort
+  if (const char* od = getenv("EVQL_ORDER_DEVICE_SORT")) {
+    if (strcmp(od, "0") == 0) q->order_device_sort = false;
+  }
   if (plan->group_mode != EVQL_MODE_FINAL && plan->group_mode != EVQL_MODE_PARTIAL) {
     return fail(EVQL_EARG, "bad group mode");
   }
@@ -901,6 +905,15 @@ int evql_query_emit_stats(const evql_query_t* q, evql_emit_stats_t* out) {
   return EVQL_OK;
 }
 
+int evql_query_order_stats(const evql_query_t* q, evql_order_stats_t* out) {
+  if (!q || !out) return fail(EVQL_EARG, "null argument");
+  if (q->kp.bare_scan || !q->executed || !q->fetched) {
+    return fail(EVQL_EARG, "no result was fetched");
+  }
+  *out = q->ostats;
+  return EVQL_OK;
+}
+
 const char* evql_query_kernel_source(const evql_query_t* q) { return q->source.c_str(); }
 
 // ---- partial aggregates ---------------------------------------------------------------
@@ -1170,6 +1183,47 @@ int evql_plan_partial_emit(const evql_plan_desc_t* plan, const evql_column_info_
   q.merged = merged != 0;
   PartialEmitPlan pplan;
   *decision = int(plan_partial_emit(partial_emit_input(&q, n_groups), &pplan));
+  return EVQL_OK;
+  API_CATCH
+}
+
+int evql_plan_order_sort(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                         int ncolumns, const evql_sort_spec_t* specs, uint32_t n_specs,
+                         uint64_t n_records, int* decision) {
+  API_TRY
+  if (!plan || (!columns && ncolumns) || (!specs && n_specs) || !decision) {
+    return fail(EVQL_EARG, "null argument");
+  }
+  TableLayout layout;
+  layout.version = 2;
+  layout.num_rows = 0;
+  for (int i = 0; i < ncolumns; ++i) {
+    ColumnLayout c;
+    c.name = columns[i].name;
+    c.logical_type = ColumnType(columns[i].logical_type);
+    c.storage_type = ColumnEncoding(columns[i].storage_type);
+    c.column_id = columns[i].column_id;
+    c.rlevel_max = columns[i].rlevel_max;
+    c.dlevel_max = columns[i].dlevel_max;
+    layout.columns.push_back(c);
+  }
+  evql_query q;
+  q.group_mode = plan->group_mode;
+  q.float_sum_mode = plan->float_sum_mode;
+  q.float_sum_bound = plan->float_sum_bound;
+  bool unsupported = false;
+  Status st = build_kernel_plan(layout, plan, &q, &unsupported);
+  if (!st.ok()) return ret(st);
+  if (q.kp.bare_scan) return fail(EVQL_EARG, "a bare scan holds no groups");
+  if (const char* od = getenv("EVQL_ORDER_DEVICE_SORT")) {
+    if (strcmp(od, "0") == 0) q.order_device_sort = false;
+  }
+  if (n_specs) {
+    st = query_set_order(&q, specs, n_specs, -1, 0);
+    if (!st.ok()) return ret(st);
+  }
+  OrderSortPlan oplan;
+  *decision = int(plan_order_sort(order_sort_input(&q, n_records), &oplan));
   return EVQL_OK;
   API_CATCH
 }

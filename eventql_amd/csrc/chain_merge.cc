@@ -186,6 +186,7 @@ Status chain_merge(evql_query* head) {
   head->stats.kernel_ms = kernel_ms;
   head->stats.total_ms = kernel_ms;
   head->fetched = false;
+  head->order_applied = false;
   head->tail_valid = false;
   head->emit_pos = 0;
   return Status();

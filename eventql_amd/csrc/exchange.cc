@@ -771,6 +771,7 @@ Status ExchangeRun::finish_merge() {
   q->ngroups = ng;
   q->stats.num_groups = ng;
   q->fetched = false;
+  q->order_applied = false;
   q->tail_valid = false;  // (the eager block holds this rank's groups before the merge)
   q->emit_pos = 0;
   x->stats.merge_ms = ms_since(t2);

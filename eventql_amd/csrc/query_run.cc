@@ -850,6 +850,7 @@ Status query_finish(evql_query* q) {
     q->stats.num_groups = q->ngroups;
     q->executed = true;
     q->fetched = false;
+    q->order_applied = false;
     q->emit_pos = 0;
     // more groups than the block takes: its records are ignored, the first next_batch
     // compacts the table (results.cc collect_records)
@@ -873,6 +874,7 @@ Status query_recount(evql_query* q) {
   q->ngroups = n + q->dense_n;
   q->stats.num_groups = q->ngroups;
   q->fetched = false;
+  q->order_applied = false;
   q->tail_valid = false;  // (the block holds the table as finish saw it)
   q->executed = true;
   q->emit_pos = 0;
@@ -1009,6 +1011,7 @@ Status query_import_pairs(evql_query* q, int which, const uint64_t* d_triples, u
     return Status::error(EVQL_EARG, "a pair's group is not in the table: import the group records first");
   }
   q->fetched = false;
+  q->order_applied = false;
   q->tail_valid = false;
   return Status();
 }
@@ -1042,6 +1045,7 @@ Status query_reset(evql_query* q) {
   q->stats.rows_passed = 0;
   q->executed = true;
   q->fetched = false;
+  q->order_applied = false;
   q->tail_valid = false;
   q->tail_armed = 0;
   q->launched = false;

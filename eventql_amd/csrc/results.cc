@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include "radix_sort.h"
 #include "runtime.h"
 #include "sha1.h"
 
@@ -18,8 +19,10 @@ namespace evql {
 // config 4 / 4s, and what `select k, count(1), sum(x) .. group by k` looks like -- one
 // kernel writes the packed SVector bytes (svalue.cc:410-517) of every column for ALL groups;
 // the host copies each column once into pinned memory and next_batch hands out slices.
-// Row order is unspecified for a GROUP BY; small results keep the host path
-// and its deterministic order.  (kDeviceEmitMinGroups: partial_emit_plan.h)
+// Row order is unspecified for a GROUP BY without ORDER BY; small results keep the
+// host path and its deterministic order.  With ORDER BY the rows come in the order of the
+// specs, ties in the order of sort_host_records, whether the host (order_fetched) or the
+// device (sort_on_device) sorted them.  (kDeviceEmitMinGroups: partial_emit_plan.h)
 
 // device time and work of one packing: evql_query_emit_stats
 struct PackMeter {
@@ -48,10 +51,13 @@ struct PackMeter {
   }
 };
 
-static bool device_emit_columns(const evql_query* q, bool merged, EmitArgs* ea) {
+// `ordered`: the records are the ORDER BY / LIMIT slice already (sort_on_device); every other
+// caller asks about a result that order_fetched would still have to reorder
+static bool device_emit_columns(const evql_query* q, bool merged, EmitArgs* ea, bool ordered = false) {
   const KernelPlan& kp = q->rplan();
   const size_t nsel = q->select.size();
-  if (q->group_mode != EVQL_MODE_FINAL || !q->order.empty() || q->has_limit) return false;
+  if (q->group_mode != EVQL_MODE_FINAL) return false;
+  if (!ordered && (!q->order.empty() || q->has_limit)) return false;
   if (nsel == 0 || nsel > kMaxEmitCols) return false;
   for (size_t i = 0; i < nsel; ++i) {
     const LoweredProgram& lp = q->select[i];
@@ -483,7 +489,9 @@ static void sort_host_records(evql_query* q, uint64_t n, uint32_t nwords) {
   q->records.swap(sorted);
 }
 
-static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t nwords) {
+// (`in_order`: the records are the sorted slice of sort_on_device and stay as they come)
+static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t nwords,
+                              bool in_order) {
   hipStream_t s = q->ctx->stream;
   q->records.assign(n * (nwords + 1), 0);
   if (n) {
@@ -491,7 +499,127 @@ static Status records_to_host(evql_query* q, const uint64_t* d_rec, uint64_t n, 
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  sort_host_records(q, n, nwords);
+  if (!in_order) sort_host_records(q, n, nwords);
+  return Status();
+}
+
+// ---------------------------------------------------------------------------
+// ORDER BY over a large result: sorted on the device
+// ---------------------------------------------------------------------------
+// order_fetched boxes every cell of every group and runs a std::stable_sort with value_cmp
+// over the records in sort_host_records order.  For the results plan_order_sort accepts the
+// same order comes out of stable LSD radix sorts over order-preserving keys, least significant
+// first: the kind word and the base word (sort_host_records' order), then the specs from the
+// last to the first.  The OFFSET / LIMIT slice is gathered in that order and emitted as it lies.
+OrderSortInput order_sort_input(const evql_query* q, uint64_t n) {
+  OrderSortInput in;
+  in.group_mode = q->group_mode;
+  in.n = n;
+  in.enabled = q->order_device_sort;
+  in.kp = &q->rplan();
+  in.select = &q->select;
+  in.select_agg_index = &q->select_agg_index;
+  in.select_passthrough = &q->select_passthrough;
+  in.order = &q->order;
+  in.order_desc = &q->order_desc;
+  return in;
+}
+
+static OrderKeyArgs order_key_args(const OrderKeySpec& k) {
+  OrderKeyArgs a{};
+  a.from_ident = k.from_ident;
+  a.word = k.word;
+  a.count_word = k.count_word;
+  a.type = k.type;
+  a.is_mean = k.is_mean;
+  a.descending = k.descending;
+  return a;
+}
+
+// rows [lo, hi) of n ordered records are the result, as order_fetched has it
+static void limit_slice(const evql_query* q, uint64_t n, uint64_t* lo, uint64_t* hi) {
+  *lo = 0;
+  *hi = n;
+  if (q->has_limit) {
+    *lo = std::min(q->offset, n);
+    *hi = q->limit == 0 ? *lo : std::min(n, q->offset + q->limit);
+    if (*hi < *lo) *hi = *lo;  // (offset + limit wrapped)
+  }
+}
+
+// step 2b: r's records become the ordered slice.  A NaN float key leaves r as it is and
+// q->ostats.decision = OSORT_NAN_KEY: value_cmp on a NaN is no order a radix sort reproduces.
+static Status sort_on_device(evql_query* q, const OrderSortPlan& plan, FetchedRecords* r) {
+  hipStream_t s = q->ctx->stream;
+  const uint64_t n = r->n;
+  const uint32_t rw = r->nwords + 1;
+  evql_order_stats_t& os = q->ostats;
+  uint64_t lo, hi;
+  limit_slice(q, n, &lo, &hi);
+  const uint64_t m = hi - lo;
+  PackMeter pm;
+  HIP_TRY(pm.begin(s));
+  // every allocation of the sort, once
+  DevBuf<uint64_t> d_keys, d_out;
+  DevBuf<uint32_t> d_idx;
+  RadixSortScratch sc;
+  HIP_TRY(d_keys.alloc(n * 8));
+  HIP_TRY(d_idx.alloc(n * 4));
+  HIP_TRY(d_out.alloc(m * rw * 8));
+  Status st = sc.alloc(n);
+  if (!st.ok()) return st;
+  HIP_TRY(hipMemsetAsync(sc.stats, 0, 4 * 8, s));
+  // least significant key first: kind, base word, specs last to first
+  const size_t ns = plan.keys.size();
+  for (size_t k = 0; k < ns + 2 && m > 0; ++k) {
+    OrdKeyPermArgs ka{};
+    if (k < 2) {
+      ka.plain_word = 1;
+      ka.key.word = k == 0 ? 0 : plan.base_word;
+    } else {
+      ka.key = order_key_args(plan.keys[ns + 1 - k]);
+    }
+    ka.key.records = r->d_rec;
+    ka.key.record_words = rw;
+    ka.key.n = n;
+    ka.key.keys = d_keys;
+    ka.perm = sc.idx_identity ? nullptr : d_idx.p;
+    ka.status = sc.stats.p + 3;
+    HIP_TRY(launch_ord_key_perm(ka, s));
+    ++sc.launches;
+    st = radix_sort_pairs(&d_keys, &d_idx, n, &sc, s, &os.n_sort_passes, &os.n_passes_skipped);
+    if (!st.ok()) return st;
+    ++os.n_keys;
+    if (sc.h_stats[3] & kOrdStatusBounds) {
+      return Status::error(EVQL_ERUNTIME, "order sort: a permutation entry outside the records");
+    }
+    if (sc.h_stats[3] & kOrdStatusNaN) {
+      os.decision = OSORT_NAN_KEY;
+      os.n_kernel_launches = sc.launches;
+      os.n_host_waits = sc.waits;
+      return Status();
+    }
+  }
+  uint64_t gather_status = 0;
+  HIP_TRY(launch_ord_gather(r->d_rec, rw, n, sc.idx_identity ? nullptr : d_idx.p, lo, m, d_out,
+                            sc.stats.p + 3, s));
+  HIP_TRY(hipMemcpyAsync(&gather_status, sc.stats.p + 3, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(pm.mark_end(s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (m) ++sc.launches;
+  ++sc.waits;
+  if (gather_status & kOrdStatusBounds) {
+    return Status::error(EVQL_ERUNTIME, "order sort: a permutation entry outside the records");
+  }
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, pm.e0, pm.e1));
+  os.sort_ms = ms;
+  os.n_kernel_launches = sc.launches;
+  os.n_host_waits = sc.waits;
+  os.sorted_on_device = 1;
+  r->own = std::move(d_out);
+  r->d_rec = r->own;
+  r->n = m;
   return Status();
 }
 
@@ -671,6 +799,23 @@ static Status fetch_results(evql_query* q) {
       if (!st.ok()) return st;
     }
   }
+  // step 2b: ORDER BY over a large result is sorted, and OFFSET / LIMIT cut, on the device
+  q->order_applied = false;
+  q->ostats = evql_order_stats_t{};
+  q->ostats.records = r.n;
+  {
+    uint64_t lo, hi;
+    limit_slice(q, r.n, &lo, &hi);
+    q->ostats.rows = hi - lo;
+    OrderSortPlan oplan;
+    q->ostats.decision = uint32_t(plan_order_sort(order_sort_input(q, r.n), &oplan));
+    if (q->ostats.decision == OSORT_DEVICE && !from_block) {
+      st = sort_on_device(q, oplan, &r);
+      if (!st.ok()) return st;
+      q->order_applied = q->ostats.sorted_on_device != 0;
+    }
+  }
+  const bool ordered = q->order_applied;
   const uint64_t n = r.n;
   q->ngroups = n;
   q->rec_stride = r.nwords + 1;
@@ -686,7 +831,7 @@ static Status fetch_results(evql_query* q) {
     q->first_vals.clear();
     q->first_tags.clear();
     q->distinct_values.clear();
-  } else if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea)) {
+  } else if (n >= kDeviceEmitMinGroups && device_emit_columns(q, q->merged, &ea, ordered)) {
     st = emit_on_device(q, ea, r.d_rec, n, r.nwords);
     if (!st.ok()) return st;
     q->records.clear();
@@ -697,7 +842,7 @@ static Status fetch_results(evql_query* q) {
     q->records.clear();
     q->distinct_values.clear();
   } else {
-    st = records_to_host(q, r.d_rec, n, r.nwords);
+    st = records_to_host(q, r.d_rec, n, r.nwords, ordered);
     if (!st.ok()) return st;
     q->first_vals.clear();
     q->first_tags.clear();
@@ -881,49 +1026,21 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
   }
   OrderKeyArgs ok{};
   if (n > 0) {
-    const KernelPlan& kp = q->rplan();
-    const ExprPtr& e0 = order[0].call;
-    if (e0->kind != Expr::INPUT) {
-      return Status::error(EVQL_ENOTSUP, "first sort expression is not a plain output column");
+    // (the classification is order_sort_plan.cc's: the device sort asks it of every spec)
+    OrderKeySpec k0{};
+    switch (classify_order_key(q->rplan(), q->select, q->select_agg_index, q->select_passthrough,
+                               order[0], desc[0], &k0)) {
+      case OKEY_RECORD:
+        break;
+      case OKEY_EXPRESSION:
+        return Status::error(EVQL_ENOTSUP, "first sort expression is not a plain output column");
+      case OKEY_EXACT_SUM:
+        return Status::error(EVQL_ENOTSUP, "ORDER BY an exact float sum is not fused");
+      default:
+        return Status::error(EVQL_ENOTSUP,
+                             "first sort expression cannot be read from a group record");
     }
-    const uint32_t si = e0->input;
-    const LoweredProgram& sp = q->select[si];
-    auto type_code = [](uint32_t t) { return t == EVQL_T_INT64 ? 1u : (t == EVQL_T_FLOAT64 ? 2u : 0u); };
-    ok.count_word = -1;
-    ok.descending = desc[0];
-    if (q->select_passthrough[si] && sp.return_type != EVQL_T_STRING) {
-      ok.from_ident = 1;
-      ok.word = 1;
-      ok.type = type_code(sp.return_type);
-    } else if (sp.is_aggregate && sp.call->kind == Expr::AGG_GET) {
-      const AggPlan& a = kp.aggs[q->select_agg_index[si]];
-      ok.word = uint32_t(1 + kp.state_word_base() + a.first_word);
-      switch (a.fn) {
-        case EVQL_AGG_COUNT:
-        case EVQL_AGG_COUNT_DISTINCT_UINT64:  // (one word: the number of distinct values)
-        case EVQL_AGG_SUM_UINT64: ok.type = 0; break;
-        case EVQL_AGG_SUM_INT64: ok.type = 1; break;
-        case EVQL_AGG_SUM_FLOAT64:
-          if (a.exact_index >= 0) {
-            return Status::error(EVQL_ENOTSUP, "ORDER BY an exact float sum is not fused");
-          }
-          ok.type = 2;
-          break;
-        case EVQL_AGG_MEAN_UINT64:
-        case EVQL_AGG_MEAN_INT64:
-        case EVQL_AGG_MEAN_FLOAT64:
-          ok.type = 2;
-          ok.is_mean = 1;
-          ok.count_word = int32_t(ok.word + 1);
-          break;
-        default:  // min / max
-          ok.type = type_code(sp.return_type);
-          ok.count_word = int32_t(ok.word + 1);
-      }
-    } else {
-      return Status::error(EVQL_ENOTSUP,
-                           "first sort expression cannot be read from a group record");
-    }
+    ok = order_key_args(k0);
   }
   q->order.swap(order);
   q->order_desc.swap(desc);
@@ -932,6 +1049,7 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
   q->offset = offset;
   q->order_key = ok;
   q->fetched = false;
+  q->order_applied = false;
   return Status();
 }
 
@@ -1150,8 +1268,13 @@ Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols,
   if (!q->fetched) {
     Status st = fetch_results(q);
     if (!st.ok()) return st;
-    st = order_fetched(q);
-    if (!st.ok()) return st;
+    // (sort_on_device left the records as the ordered slice already)
+    if (q->order_applied) {
+      q->emit_order.clear();
+    } else {
+      st = order_fetched(q);
+      if (!st.ok()) return st;
+    }
   }
   if (q->demit.active) {
     // slices of the columns packed on the device (emit_on_device)
@@ -1187,7 +1310,7 @@ Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols,
   size_t emitted = 0;
   std::vector<Value> scan_vals, sel_inputs;
   const std::vector<Value> none;
-  const bool reordered = !q->order.empty() || q->has_limit;
+  const bool reordered = !q->order_applied && (!q->order.empty() || q->has_limit);
   const uint64_t emit_total = reordered ? q->emit_order.size() : q->ngroups;
   while (q->emit_pos < emit_total && emitted < max_rows) {
     const uint64_t g = reordered ? q->emit_order[q->emit_pos] : q->emit_pos;

@@ -14,6 +14,7 @@
 #include "codegen.h"
 #include "cstable_format.h"
 #include "materialize_plan.h"
+#include "order_sort_plan.h"
 #include "plan_ir.h"
 
 namespace evql {
@@ -500,6 +501,11 @@ struct evql_query {
   uint64_t limit = 0, offset = 0;
   evql::OrderKeyArgs order_key{};     // where the device finds sort key 0 in a record
   std::vector<uint64_t> emit_order;  // record indices in output order (when ordered)
+  // ORDER BY over a large result sorted on the device (results.cc sort_on_device)
+  bool order_device_sort = true;  // EVQL_ORDER_DEVICE_SORT, read when the operator is created
+  bool order_applied = false;     // the fetched records are the ordered OFFSET / LIMIT slice:
+                                  // order_fetched does not run; cleared wherever `fetched` is
+  evql_order_stats_t ostats{};    // how the last fetched result was ordered
   evql_query_stats_t stats{};
   ~evql_query();
 };
@@ -653,6 +659,8 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
 Status query_next_batch(evql_query* q, size_t max_rows, evql_column_buf_t* cols, size_t* nrows);
 // what plan_partial_emit (partial_emit_plan.h) decides on for a result of n groups of q
 PartialEmitInput partial_emit_input(const evql_query* q, uint64_t n);
+// what plan_order_sort (order_sort_plan.h) decides on for n records of q entering the sort
+OrderSortInput order_sort_input(const evql_query* q, uint64_t n);
 // the groups as dense device records [kind, slot words...] on their way to the host or to the
 // device writer (materialize.cc)
 struct FetchedRecords {

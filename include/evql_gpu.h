@@ -629,6 +629,32 @@ typedef struct {
 } evql_emit_stats_t;
 int evql_query_emit_stats(const evql_query_t* q, evql_emit_stats_t* out);
 
+/* How the last fetched result was ordered (evql_query_set_order).  With at least 65,536
+ * records entering the sort (after the top-k selection of ORDER BY .. LIMIT, if it ran), at
+ * most 8 sort specs and every spec a select column a group record holds -- the non-string
+ * group key, a bare count, count_distinct, integer sum, fast float sum, mean, min or max --
+ * the device sorts the records and cuts OFFSET / LIMIT; the environment variable
+ * EVQL_ORDER_DEVICE_SORT=0, read when the query is created, keeps the host's sort.  Rows,
+ * their order (ties included) and their bytes are the same either way.  `decision`: 0 sorted
+ * on the device, 1 no sort spec (or PARTIAL mode), 2 fewer than 65,536 records, 3 switched
+ * off, 4 a spec is an expression, 5 a spec column cannot be read from a record (a string, a
+ * first-row column, post-aggregate arithmetic, an exact float sum), 6 more than 8 specs,
+ * 7 2^32 records or more, 8 a float sort key was NaN (the host ordered).  EVQL_EARG before a
+ * result was fetched, and for a bare scan. */
+typedef struct {
+  uint32_t sorted_on_device;   /* 1: ordered and cut by kernels; 0: by the host */
+  uint32_t decision;
+  uint64_t records;            /* records entering the sort */
+  uint64_t rows;               /* rows after OFFSET / LIMIT */
+  uint32_t n_keys;             /* sorts run: the specs and the two words of the base order */
+  uint32_t n_sort_passes;      /* 8-bit digit passes run over all keys */
+  uint32_t n_passes_skipped;   /* ... and not needed (keys in order already, high digits equal) */
+  uint32_t n_kernel_launches;  /* of the sort (0 on the host path) */
+  uint32_t n_host_waits;
+  double sort_ms;              /* device time from the first key kernel to the gathered slice */
+} evql_order_stats_t;
+int evql_query_order_stats(const evql_query_t* q, evql_order_stats_t* out);
+
 /* the generated HIP source of the fused kernel (inspection / tests) */
 const char* evql_query_kernel_source(const evql_query_t* q);
 
@@ -861,11 +887,14 @@ int evql_merge_index_frame(const evql_plan_desc_t* plan, const void* payload, si
  * into the operator so that a high-cardinality GROUP BY does not ship every
  * group through nextBatch: the device selects the offset+limit smallest records
  * by the first sort key (radix select over the group table), only those are
- * fetched, and the host orders them by all specs.  Sort expressions are programs
- * over the query's OUTPUT columns (X_INPUT i = select expression i), compared with
- * the reference's cmp#int64/X;X; comparators: payloads only, NULL reads as 0, ties
- * in unspecified order (the reference uses std::sort).  limit < 0: ORDER BY
- * only.  limit == 0 yields no rows (limit.cc:58).  Call before execute().
+ * fetched.  What is fetched is ordered by all specs: on the device when 65,536
+ * records or more enter the sort and every spec is a select column that a group
+ * record holds (stable radix sorts over order-preserving keys, then the OFFSET /
+ * LIMIT slice; evql_query_order_stats), by the host otherwise.  Sort expressions
+ * are programs over the query's OUTPUT columns (X_INPUT i = select expression i),
+ * compared with the reference's cmp#int64/X;X; comparators: payloads only, NULL
+ * reads as 0, ties in unspecified order (the reference uses std::sort; in fact
+ * both paths leave ties in the same order).  limit < 0: ORDER BY only.  limit == 0 yields no rows (limit.cc:58).  Call before execute().
  * EVQL_ENOTSUP when the first sort expression is not a select column whose value
  * the device can read from a group record (the group key, or a bare count / sum /
  * min / max / mean): the caller then keeps the CPU operators above this one.
@@ -1146,6 +1175,14 @@ int evql_ctx_sha1_ranges(evql_ctx_t* ctx, const void* bytes, size_t len, const u
  * float sum, 7 more than 32 columns, 8 a NIL-typed column, 9 a nested scan). */
 int evql_plan_partial_emit(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
                            int ncolumns, uint64_t n_groups, int merged, int* decision);
+
+/* Would `n_records` records of `plan` under ORDER BY `specs` be sorted on the device
+ * (evql_query_order_stats)?  No device needed; columns as for evql_compile_only.  *decision as
+ * evql_order_stats_t.decision.  Specs that evql_query_set_order refuses are refused here with
+ * the same code and message. */
+int evql_plan_order_sort(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                         int ncolumns, const evql_sort_spec_t* specs, uint32_t n_specs,
+                         uint64_t n_records, int* decision);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,14 @@ class GpuGroupByScan : public TableExpression {
     return e;
   }
 
+  // how the last fetched result was ordered (evql_query_order_stats): on the device for large
+  // results whose sort specs are record-readable select columns; throws like emitStats()
+  evql_order_stats_t orderStats() const {
+    evql_order_stats_t o{};
+    if (evql_query_order_stats(query_, &o) != EVQL_OK) throw std::runtime_error(evql_last_error());
+    return o;
+  }
+
   // The groups of the executed operator as a resident cstable, written on the device
   // (evql_table_from_query): the inner statement of a SubqueryNode stays in HBM, the outer
   // operator is created over the returned table, which the caller closes (evql_table_close).
