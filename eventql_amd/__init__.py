@@ -165,6 +165,8 @@ def lib():
     L.evql_set_kernel_cache_dir.argtypes = [C.c_char_p]
     L.evql_compile_only.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(K.ColumnInfo), C.c_int,
                                     C.c_char_p, C.POINTER(C.c_size_t)]
+    L.evql_plan_kernel_text.argtypes = [C.POINTER(K.PlanDesc), C.POINTER(K.ColumnInfo), C.c_int,
+                                        C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.evql_set_kernel_cache_dir(KERNEL_CACHE_DIR.encode())
     _lib = L
     return L
@@ -806,6 +808,18 @@ def compile_only(plan, columns, cache_dir=None):
     cd = (cache_dir or KERNEL_CACHE_DIR).encode()
     _check(lib().evql_compile_only(C.byref(plan.desc), infos, len(columns), cd, C.byref(size)))
     return size.value
+
+
+def plan_kernel_text(plan, columns):
+    """the text compile_only would compile for `plan` over `columns` (Query.kernel_source of a
+    query over such a table); nothing is compiled, no device needed"""
+    infos = _column_infos(columns)
+    n = C.c_size_t()
+    _check(lib().evql_plan_kernel_text(C.byref(plan.desc), infos, len(columns), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(n.value + 1)
+    _check(lib().evql_plan_kernel_text(C.byref(plan.desc), infos, len(columns), buf, n.value + 1,
+                                       C.byref(n)))
+    return buf.value.decode()
 
 
 def kernel_cache_stats():

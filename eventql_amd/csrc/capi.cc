@@ -1079,10 +1079,11 @@ int evql_query_set_order(evql_query_t* q, const evql_sort_spec_t* specs, uint32_
 // ---- build support ------------------------------------------------------------------------
 void evql_set_kernel_cache_dir(const char* dir) { set_cache_dir(dir ? dir : ""); }
 
-int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* columns, int ncolumns,
-                      const char* cache_dir, size_t* code_size) {
-  API_TRY
-  if (cache_dir) set_cache_dir(cache_dir);
+// the kernel plan and the generated text of `plan` over `columns`, as evql_compile_only and
+// evql_plan_kernel_text see them: no table, no device
+static Status plan_text_without_table(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                                      int ncolumns, evql_query* qp) {
+  evql_query& q = *qp;
   TableLayout layout;
   layout.version = 2;
   layout.num_rows = 0;
@@ -1096,10 +1097,9 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
     c.dlevel_max = columns[i].dlevel_max;
     layout.columns.push_back(c);
   }
-  evql_query q;
   bool unsupported = false;
   Status st = build_kernel_plan(layout, plan, &q, &unsupported);
-  if (!st.ok()) return ret(st);
+  if (!st.ok()) return st;
   // bit widths are not known without pages: payload_bytes carries the width.  On a required
   // UINT64_PLAIN / UINT64_LEB128 column a width of 8 / 16 / 32 asks for the shape over the
   // flat narrow copy a resident table keeps of it (query_prepare makes the same switch).
@@ -1132,10 +1132,37 @@ int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* co
   // (the access modes changed: the launch shape is chosen again, as query_prepare does)
   if (repacked && !q.kp.partitioned) choose_launch_shape(&q.kp, plan->groups_hint);
   q.source = generate_kernel_source(&q.kp);
+  return Status();
+}
+
+int evql_compile_only(const evql_plan_desc_t* plan, const evql_column_info_t* columns, int ncolumns,
+                      const char* cache_dir, size_t* code_size) {
+  API_TRY
+  if (cache_dir) set_cache_dir(cache_dir);
+  evql_query q;
+  Status st = plan_text_without_table(plan, columns, ncolumns, &q);
+  if (!st.ok()) return ret(st);
   std::vector<char> code;
   st = compile_to_code_object(q.source, &code, true);
   if (!st.ok()) return ret(st);
   if (code_size) *code_size = code.size();
+  return EVQL_OK;
+  API_CATCH
+}
+
+int evql_plan_kernel_text(const evql_plan_desc_t* plan, const evql_column_info_t* columns, int ncolumns,
+                          char* text, size_t capacity, size_t* length) {
+  API_TRY
+  if (!plan || !length || (!text && capacity)) return fail(EVQL_EARG, "null argument");
+  evql_query q;
+  Status st = plan_text_without_table(plan, columns, ncolumns, &q);
+  if (!st.ok()) return ret(st);
+  *length = q.source.size();
+  if (capacity) {
+    const size_t n = std::min(capacity - 1, q.source.size());
+    memcpy(text, q.source.data(), n);
+    text[n] = '\0';
+  }
   return EVQL_OK;
   API_CATCH
 }

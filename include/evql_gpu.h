@@ -1155,6 +1155,12 @@ int evql_plan_materialize(const evql_plan_desc_t* plan, const evql_column_info_t
 int evql_compile_only(const evql_plan_desc_t* plan,
                       const evql_column_info_t* columns, int ncolumns,
                       const char* cache_dir, size_t* code_size);
+/* The text evql_compile_only would compile for `plan` over `columns` (what
+ * evql_query_kernel_source returns for a query over such a table), without compiling it: no
+ * device needed.  *length = its length in bytes; `text` receives at most capacity - 1 of them
+ * and a terminating 0 (capacity 0, text NULL: the length alone). */
+int evql_plan_kernel_text(const evql_plan_desc_t* plan, const evql_column_info_t* columns,
+                          int ncolumns, char* text, size_t capacity, size_t* length);
 /* on-disk cache of the compiled plan kernels (code objects named by the fingerprint of
  * their source).  Default: the directory `_kcache` next to this shared library, shared by
  * every process that loads it; "" switches the disk cache off. */
