@@ -26,6 +26,20 @@ __device__ __forceinline__ u8 vbyte_fwd(const u8* image, const u64* pages, u64 p
   return image[pages[pos >> 19] + (pos & 0x7ffffull)];
 }
 
+// the byte sources of put_string_elem (result_cell.h): a string at `off` of a column's paged
+// byte stream, and one at `pos` of an arena of `len` bytes (0 behind its end)
+struct PagedBytes {
+  const u8* image;
+  const uint64_t* pages;
+  u64 off;
+  __device__ __forceinline__ u8 operator()(u32 k) const { return vbyte_fwd(image, (const u64*) pages, off + k); }
+};
+struct ArenaBytes {
+  const u8* arena;
+  u64 len, pos;
+  __device__ __forceinline__ u8 operator()(u32 k) const { return pos + k < len ? arena[pos + k] : (u8) 0; }
+};
+
 // ---- table maintenance -----------------------------------------------------------
 __global__ void k_table_init(TableInitArgs a) {
   // slots of `nwords` adjacent words
@@ -1576,19 +1590,11 @@ __global__ void k_copy_strings(const u8* image, const u64* pages, const u64* str
 // ---- ORDER BY .. LIMIT ----------------------------------------------------------------
 // the order-preserving key of one record; *nan: the float value is a NaN (cmp_float64 has no
 // order for it)
-__device__ __forceinline__ u64 order_key(const OrderKeyArgs& a, const u64* rec, bool* nan) {
-  u64 v = rec[a.word];
-  if (a.from_ident) {
-    // kind 2 = NULL key: payload 0 (the comparators ignore tags)
-    if (rec[0] == 2) v = 0;
-  } else if (a.count_word >= 0) {
-    const u64 cnt = rec[a.count_word];
-    if (cnt == 0) {
-      v = 0;
-    } else if (a.is_mean) {
-      v = evql_f64_bits(evql_as_f64(v) / (double) cnt);
-    }
-  }
+__device__ __forceinline__ u64 order_key(const OrderKeyArgs& a, const uint64_t* rec, bool* nan) {
+  // a NULL reads payload 0 (the comparators ignore tags).  A sort key is the group key or a
+  // state (classify_order_key); there are no first-row arrays here to read another from
+  bool null = false;
+  u64 v = a.kind == 2 ? 0 : cell_bits(a, rec, nullptr, nullptr, 0, 0, &null);
   u64 key;
   *nan = false;
   if (a.type == 0) {
@@ -1607,7 +1613,7 @@ __global__ void __launch_bounds__(kBlock) k_order_keys(OrderKeyArgs a) {
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < a.n;
        i += (u64) gridDim.x * blockDim.x) {
     bool nan;
-    a.keys[i] = order_key(a, (const u64*) a.records + i * a.record_words, &nan);
+    a.keys[i] = order_key(a, a.records + i * a.record_words, &nan);
   }
 }
 
@@ -1622,7 +1628,7 @@ __global__ void __launch_bounds__(kBlock) k_ord_key_perm(OrdKeyPermArgs a) {
     if (r >= a.key.n) {
       atomicOr((unsigned long long*) a.status, (unsigned long long) kOrdStatusBounds);
     } else {
-      const u64* rec = (const u64*) a.key.records + r * a.key.record_words;
+      const uint64_t* rec = a.key.records + r * a.key.record_words;
       if (a.plain_word) {
         key = rec[a.key.word];
       } else {
@@ -2330,31 +2336,13 @@ __global__ void __launch_bounds__(kBlock) k_emit_fixed(const EmitArgs* ap, u64 n
   const EmitArgs& a = *ap;
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.rw;
+    const uint64_t* rec = a.records + i * a.rw;
     for (u32 c = 0; c < a.ncols; ++c) {
       const EmitCol& e = a.col[c];
       if (e.elem == 0) continue;  // strings: k_emit_str_*
-      u64 bits = 0;
-      u8 tag = 0;
-      if (e.kind == 0) {
-        if (rec[0] == 2) tag = kStagNull; else bits = rec[1];
-      } else if (e.kind == 1) {
-        bits = rec[e.word];
-        if (e.count_word >= 0) {
-          const u64 cnt = rec[e.count_word];
-          if (cnt == 0) {
-            bits = 0;
-            tag = kStagNull;
-          } else if (e.is_mean) {
-            const double m = evql_as_f64(bits) / (double) cnt;
-            bits = evql_f64_bits(m);
-          }
-        }
-      } else {
-        const u64 raw = ((const u64*) a.first_vals)[(u64) e.src * n + i];
-        tag = a.first_tags[(u64) e.src * n + i] & 1 ? kStagNull : 0;
-        bits = e.to_float ? evql_f64_bits((double) raw) : raw;
-      }
+      bool null;
+      const u64 bits = cell_bits(e, rec, a.first_vals, a.first_tags, n, i, &null);
+      const u8 tag = null ? kStagNull : 0;
       if (e.elem == 2) {  // BOOL: value byte, tag byte
         e.out[i * 2] = (u8) (bits != 0);
         e.out[i * 2 + 1] = tag;
@@ -2386,10 +2374,7 @@ __global__ void __launch_bounds__(kBlock) k_emit_str_bytes(const EmitArgs* ap, u
     const u64 sp = ((const u64*) a.first_vals)[(u64) e.src * n + i];
     const u32 len = null ? 0u : (u32) (sp >> 40);
     const u64 off = sp & kStrOffMask;
-    u8* p = e.out + ((const u64*) e.offsets)[i];
-    p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
-    for (u32 k = 0; k < len; ++k) p[4 + k] = vbyte_fwd(a.image, (const u64*) e.pages, off + k);
-    p[4 + len] = null ? kStagNull : 0;
+    put_string_elem(e.out + e.offsets[i], len, null ? kStagNull : (u8) 0, PagedBytes{a.image, e.pages, off});
   }
 }
 
@@ -2413,39 +2398,19 @@ __global__ void __launch_bounds__(kBlock) k_mat_fixed(const MatArgs* ap, u64 n) 
   const MatArgs& a = *ap;
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.rw;
+    const uint64_t* rec = a.records + i * a.rw;
     u32 null_in_required = 0;
     for (u32 c = 0; c < a.ncols; ++c) {
       const MatCol& e = a.col[c];
-      u64 bits = 0;
-      bool null = false;
-      if (e.kind == 0) {
-        if (rec[0] == 2) null = true; else bits = rec[1];
-      } else if (e.kind == 1) {
-        bits = rec[e.word];
-        if (e.count_word >= 0) {
-          const u64 cnt = rec[e.count_word];
-          if (cnt == 0) {
-            bits = 0;
-            null = true;
-          } else if (e.is_mean) {
-            const double m = evql_as_f64(bits) / (double) cnt;
-            bits = evql_f64_bits(m);
-          }
-        }
-      } else {
-        const u64 raw = ((const u64*) a.first_vals)[(u64) e.src * n + i];
-        null = a.first_tags[(u64) e.src * n + i] & 1;
-        bits = e.to_float ? evql_f64_bits((double) raw) : raw;
-      }
+      bool null;
+      const u64 bits = cell_bits(e, rec, a.first_vals, a.first_tags, n, i, &null);
       if (e.nulls) {
         e.nulls[i] = null ? 1 : 0;
       } else if (null) {
         null_in_required |= 1u << c;
       }
       if (e.is_string) continue;  // the value word: k_mat_str_bytes
-      if (null) bits = 0;
-      e.values[i] = e.is_bool ? (u64) (bits != 0) : bits;
+      e.values[i] = null ? 0 : bits;  // (a NULL first-row value keeps its gathered word: not here)
     }
     if (null_in_required) atomicOr((unsigned long long*) &a.status[0], (unsigned long long) null_in_required);
   }
@@ -2500,6 +2465,7 @@ __global__ void __launch_bounds__(kBlock) k_mat_str_bytes(const MatArgs* ap, u32
 // ---- EVQL_MODE_PARTIAL rows on the device (results.cc emit_partial_on_device) ----------
 // One thread per group everywhere; sizes and bytes come from the same two helpers, so every
 // store lies inside the group's scanned range.
+// (bytes of LEB128(v): of a saved state here, of a column value in the device writer)
 __device__ __forceinline__ u32 varuint_len(u64 v) {
   return v == 0 ? 1u : (u32) ((64 - __clzll((long long) v) + 6) / 7);
 }
@@ -2525,25 +2491,15 @@ __device__ __forceinline__ u32 pcell_size(const PartialArgs& a, const PartialCel
 
 // ... and the element itself.  boxed: the cell leaves through SValue::encode, where a value of
 // exactly 16 bytes -- a string of 11 -- keeps STAG_INLINE (bit 7) in its tag (svalue.cc:346-368)
-__device__ __forceinline__ u32 pcell_write(const PartialArgs& a, const PartialCell& c, const u64* rec,
+__device__ __forceinline__ u32 pcell_write(const PartialArgs& a, const PartialCell& c, const uint64_t* rec,
                                            u64 i, u8* p, bool boxed) {
-  u64 bits = 0;
-  u8 tag = 0;
-  if (c.kind == 0) {
-    if (rec[0] == 2) tag = kStagNull; else bits = rec[1];
-  } else {
-    const u64 raw = ((const u64*) a.first_vals)[(u64) c.src * a.n + i];
-    tag = a.first_tags[(u64) c.src * a.n + i] & 1 ? kStagNull : 0;
-    if (c.is_string) {
-      const u32 len = tag ? 0u : (u32) (raw >> 40);
-      const u64 off = raw & kStrOffMask;
-      p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
-      for (u32 k = 0; k < len; ++k) p[4 + k] = vbyte_fwd(a.image, (const u64*) c.pages, off + k);
-      if (boxed && len == 11) tag |= 0x80;
-      p[4 + len] = tag;
-      return 5 + len;
-    }
-    bits = c.to_float ? evql_f64_bits((double) raw) : raw;
+  bool null;
+  const u64 bits = cell_bits(c, rec, a.first_vals, a.first_tags, a.n, i, &null);
+  u8 tag = null ? kStagNull : 0;
+  if (c.is_string) {  // (bits: the strpos word)
+    const u32 len = null ? 0u : (u32) (bits >> 40);
+    if (boxed && len == 11) tag |= 0x80;
+    return put_string_elem(p, len, tag, PagedBytes{a.image, c.pages, bits & kStrOffMask});
   }
   if (c.is_bool) {
     p[0] = (u8) (bits != 0);
@@ -2561,7 +2517,7 @@ __global__ void __launch_bounds__(kBlock) k_partial_sizes(const PartialArgs* ap,
   const PartialArgs& a = *ap;
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.rw;
+    const uint64_t* rec = a.records + i * a.rw;
     u64 ts = 0;
     for (u32 c = 0; c < a.n_tuple; ++c) ts += pcell_size(a, a.tuple[c], i);
     u64 ds = 5;  // u32 length in front, the tag behind
@@ -2572,7 +2528,7 @@ __global__ void __launch_bounds__(kBlock) k_partial_sizes(const PartialArgs* ap,
         // min / max / mean = varuint(count) + 8 bytes
         if (e.state == PSTATE_VARUINT) ds += varuint_len(rec[e.word]);
         else if (e.state == PSTATE_RAW8) ds += 8;
-        else ds += varuint_len(rec[e.word + 1]) + 8;
+        else ds += varuint_len(rec[e.count_word]) + 8;
       } else {
         // SValue::encode: u8 type, varuint(element bytes), the element
         const u32 el = pcell_size(a, e, i);
@@ -2589,7 +2545,7 @@ __global__ void __launch_bounds__(kBlock) k_partial_tuple_bytes(const PartialArg
   const PartialArgs& a = *ap;
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.rw;
+    const uint64_t* rec = a.records + i * a.rw;
     u8* p = heap + tuple_off[i];
     for (u32 c = 0; c < a.n_tuple; ++c) p += pcell_write(a, a.tuple[c], rec, i, p, false);
   }
@@ -2600,7 +2556,7 @@ __global__ void __launch_bounds__(kBlock) k_partial_data_bytes(const PartialArgs
   const PartialArgs& a = *ap;
   for (u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (u64) gridDim.x * blockDim.x) {
-    const u64* rec = (const u64*) a.records + i * a.rw;
+    const uint64_t* rec = a.records + i * a.rw;
     u8* p = out + data_off[i];
     const u32 len = (u32) (data_off[i + 1] - data_off[i] - 5);  // (data_off[n] = the total)
     p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
@@ -2618,7 +2574,7 @@ __global__ void __launch_bounds__(kBlock) k_partial_data_bytes(const PartialArgs
         if (e.state == PSTATE_COUNT_RAW8) {
           // a group without a non-NULL value: the word still holds the operation's identity,
           // on the wire an untouched state is 0
-          const u64 cnt = rec[e.word + 1];
+          const u64 cnt = rec[e.count_word];
           p += put_varuint(p, cnt);
           if (cnt == 0) bits = 0;
         }
@@ -3924,18 +3880,13 @@ __global__ void __launch_bounds__(kBlock) k_wr_plain(u8* image, const u64* pages
   }
 }
 
-__device__ __forceinline__ u32 wr_leb_len(u64 v) {
-  const u32 nbits = v ? 64 - (u32) __clzll((long long) v) : 1;
-  return (nbits + 6) / 7;
-}
-
 // LEB128PageWriter (page_writer_leb128.cc): bytes per 2048-value chunk ...
 __global__ void __launch_bounds__(kBlock) k_wr_leb_count(const u64* dense, u64 n,
                                                          u64* chunk_bytes) {
   const u64 i0 = (u64) blockIdx.x * kDecodeTile + (u64) threadIdx.x * 8;
   u32 len = 0;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) len += i0 + j < n ? wr_leb_len(dense[i0 + j]) : 0;
+  for (int j = 0; j < 8; ++j) len += i0 + j < n ? varuint_len(dense[i0 + j]) : 0;
   u32 total;
   block_excl_scan(len, &total);
   if (threadIdx.x == 0) chunk_bytes[blockIdx.x] = total;
@@ -3948,7 +3899,7 @@ __global__ void __launch_bounds__(kBlock) k_wr_leb_emit(u8* image, const u64* pa
   const u64 i0 = (u64) blockIdx.x * kDecodeTile + (u64) threadIdx.x * 8;
   u32 len = 0;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) len += i0 + j < n ? wr_leb_len(dense[i0 + j]) : 0;
+  for (int j = 0; j < 8; ++j) len += i0 + j < n ? varuint_len(dense[i0 + j]) : 0;
   // the chunk's bytes are contiguous in the stream: staged in LDS (shifted by the
   // chunk's misalignment so that LDS words and stream words coincide), then
   // stored as whole 32-bit words -- 4-aligned stream positions never straddle a
@@ -4048,15 +3999,6 @@ __global__ void __launch_bounds__(kBlock) k_wr_str_emit(u8* image, const u64* pa
 // a binary search over the scanned per-tile counts, then the 2048 entries of one tile
 // split over the 64 lanes (32 each: local count, wave prefix sum, the owning lane walks
 // its 32 entries).
-__device__ __forceinline__ u32 wave_incl_scan(u32 v, u32 lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 t = __shfl_up(v, d, 64);
-    if ((int) lane >= d) v += t;
-  }
-  return v;
-}
-
 // select: position of the q-th (0-based) zero byte of flags[0..n)
 __global__ void __launch_bounds__(kBlock) k_wr_select_zero(const u8* flags, u64 n,
                                                            const u64* tile_offsets, u64 ntiles,
@@ -4073,7 +4015,7 @@ __global__ void __launch_bounds__(kBlock) k_wr_select_zero(const u8* flags, u64 
   const u64 i0 = lo * kDecodeTile + (u64) lane * 32;
   u32 cnt = 0;
   for (u32 j = 0; j < 32; ++j) cnt += (i0 + j < n && flags[i0 + j] == 0) ? 1u : 0u;
-  const u32 incl = wave_incl_scan(cnt, lane);
+  const u32 incl = wave_incl_scan(cnt);
   const u64 before = tile_offsets[lo] + incl - cnt;  // zeros before this lane's entries
   u64 pos = ~0ull;
   if (q >= before && q < before + cnt) {
@@ -4129,7 +4071,7 @@ __global__ void __launch_bounds__(kBlock) k_wr_select_byte(const u64* dense, u64
   const u64 i0 = lo * kDecodeTile + (u64) lane * 32;
   u32 bytes = 0;
   for (u32 j = 0; j < 32; ++j) {
-    if (i0 + j < n) bytes += is_string ? wr_str_size(dense[i0 + j]) : wr_leb_len(dense[i0 + j]);
+    if (i0 + j < n) bytes += is_string ? wr_str_size(dense[i0 + j]) : varuint_len(dense[i0 + j]);
   }
   // (a chunk's bytes may pass 2^32 for long strings: 64-bit prefix)
   u64 incl = bytes;
@@ -4144,7 +4086,7 @@ __global__ void __launch_bounds__(kBlock) k_wr_select_byte(const u64* dense, u64
     u64 pos = before;
     for (u32 j = 0; j < 32; ++j) {
       if (i0 + j >= n) break;
-      const u64 len = is_string ? wr_str_size(dense[i0 + j]) : wr_leb_len(dense[i0 + j]);
+      const u64 len = is_string ? wr_str_size(dense[i0 + j]) : varuint_len(dense[i0 + j]);
       if (q < pos + len) { idx = i0 + j; break; }
       pos += len;
     }
@@ -4583,10 +4525,7 @@ __global__ void __launch_bounds__(kBlock) k_mrg_cell_str_bytes(MrgCellArgs a) {
     const u32 len = (u32) (w[0] >> 40);
     const u64 pos = w[0] & kStrOffMask, off = a.offsets[i];
     if (off + 5 + len > a.out_cap) continue;
-    u8* p = a.out + off;
-    p[0] = (u8) len; p[1] = (u8) (len >> 8); p[2] = (u8) (len >> 16); p[3] = (u8) (len >> 24);
-    for (u32 k = 0; k < len; ++k) p[4 + k] = pos + k < a.arena_len ? a.arena[pos + k] : (u8) 0;
-    p[4 + len] = (u8) (w[1] >> 8);
+    put_string_elem(a.out + off, len, (u8) (w[1] >> 8), ArenaBytes{a.arena, a.arena_len, pos});
   }
 }
 

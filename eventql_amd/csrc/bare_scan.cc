@@ -46,17 +46,6 @@ struct HostArgsWithScan {
 // device and pinned staging of one window, each
 const uint64_t kWindowBytes = 256ull << 20;
 
-Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap && *p) return Status();
-  if (*p) hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = bytes + bytes / 8 + 4096;
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(p), want, hipHostMallocDefault));
-  *cap = want;
-  return Status();
-}
-
 Status status_error(uint32_t st) {
   if (st & 1u) return Status::error(EVQL_ERUNTIME, "division by zero");
   if (st & 4u) return Status::error(EVQL_ERUNTIME, "modulo by zero");
@@ -251,50 +240,26 @@ static Status load_window(evql_query* q) {
 
   // the columns as SVector bytes (svalue.cc:410-517): fixed-width columns by one kernel,
   // strings by sizes -> scan -> byte copy
-  evql_query::DeviceEmit& de = q->demit;
-  de.col.resize(ncols, nullptr);
-  de.col_cap.resize(ncols, 0);
-  de.off.resize(ncols, nullptr);
-  de.off_cap.resize(ncols, 0);
-  de.elem.assign(ncols, 0);
   EmitArgs ea{};
   ea.n = n;
   ea.ncols = ncols;
   ea.first_vals = b.d_words;
   ea.first_tags = b.d_tags;
   ea.image = t->d_image;
-  std::vector<DevBuf<uint8_t>> d_out(ncols);
-  std::vector<DevBuf<uint64_t>> d_off(ncols);
-  std::vector<uint64_t> str_bytes(ncols, 0);
-  DevBuf<EmitArgs> d_args;
-  HIP_TRY(d_args.alloc(sizeof(EmitArgs)));
   for (uint32_t i = 0; i < ncols; ++i) {
     EmitCol& e = ea.col[i];
     e = EmitCol{};
     e.kind = 2;  // the value words the scan wrote, column i of [ncols][n]
     e.src = i;
-    e.count_word = -1;
     e.stype = kp.scan_out[i]->type;
-    e.elem = e.stype == EVQL_T_STRING ? 0 : (e.stype == EVQL_T_BOOL ? 2 : 9);
-    de.elem[i] = e.elem;
-    if (e.elem) {
-      HIP_TRY(d_out[i].alloc(n * e.elem));
-      e.out = d_out[i];
-    } else {
-      e.pages = t->d_pages[kp.cols[kp.scan_out[i]->input].layout_index][0];
-      HIP_TRY(d_off[i].alloc((n + 2) * 8));
-    }
+    e.is_string = e.stype == EVQL_T_STRING;
+    e.is_bool = e.stype == EVQL_T_BOOL;
+    e.elem = e.is_string ? 0 : (e.is_bool ? 2 : 9);
+    if (e.is_string) e.pages = t->d_pages[kp.cols[kp.scan_out[i]->input].layout_index][0];
   }
-  HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
-  if (n) HIP_TRY(launch_emit_fixed(d_args, n, s));
-  bool strings = false;
-  for (uint32_t i = 0; i < ncols; ++i) {
-    if (ea.col[i].elem) continue;
-    strings = true;
-    if (n) HIP_TRY(launch_emit_str_sizes(d_args, i, n, d_off[i], s));
-    HIP_TRY(launch_exclusive_scan(d_off[i], n, d_off[i].p + n, s));
-    HIP_TRY(hipMemcpyAsync(&str_bytes[i], d_off[i].p + n, 8, hipMemcpyDeviceToHost, s));
-  }
+  EmitColumnsJob job;
+  Status stb = emit_columns_begin(q, &ea, &job);
+  if (!stb.ok()) return stb;
   uint32_t status[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(status, q->d_status, 16, hipMemcpyDeviceToHost, s));
   if (b.hb) {
@@ -313,31 +278,8 @@ static Status load_window(evql_query* q) {
   // raised by a select expression of a passing row of this window
   Status se = status_error(status[0]);
   if (!se.ok()) return se;
-  if (strings) {
-    for (uint32_t i = 0; i < ncols; ++i) {
-      if (ea.col[i].elem) continue;
-      HIP_TRY(d_out[i].alloc(str_bytes[i] + 16));
-      ea.col[i].out = d_out[i];
-      ea.col[i].offsets = d_off[i];
-    }
-    HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
-    for (uint32_t i = 0; i < ncols; ++i) {
-      if (!ea.col[i].elem && n) HIP_TRY(launch_emit_str_bytes(d_args, i, n, s));
-    }
-  }
-  for (uint32_t i = 0; i < ncols; ++i) {
-    const size_t bytes = ea.col[i].elem ? size_t(n) * ea.col[i].elem : size_t(str_bytes[i]);
-    Status st = pinned_reserve(&de.col[i], &de.col_cap[i], bytes);
-    if (!st.ok()) return st;
-    if (bytes) HIP_TRY(hipMemcpyAsync(de.col[i], d_out[i], bytes, hipMemcpyDeviceToHost, s));
-    if (!ea.col[i].elem) {
-      uint8_t* po = reinterpret_cast<uint8_t*>(de.off[i]);
-      st = pinned_reserve(&po, &de.off_cap[i], (n + 1) * 8);
-      de.off[i] = reinterpret_cast<uint64_t*>(po);
-      if (!st.ok()) return st;
-      HIP_TRY(hipMemcpyAsync(de.off[i], d_off[i], (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    }
-  }
+  stb = emit_columns_finish(q, &ea, &job);
+  if (!stb.ok()) return stb;
   HIP_TRY(hipStreamSynchronize(s));
   float ms = 0;
   hipEventElapsedTime(&ms, q->ev0, q->ev1);

@@ -39,6 +39,7 @@
 // must know (the flat total as a check against the chain's own counts, the slot totals of
 // repeated columns) and, when there is a string column, one for the heap sizes.
 #include "chain_compact_plan.h"
+#include "radix_sort.h"
 #include "runtime.h"
 
 namespace evql {
@@ -76,9 +77,7 @@ struct SortJob {
   bool own_wait = false;          // no STRING column: the statistics need a wait of their own
   DevBuf<uint64_t> d_stats;       // [0..2] k_sort_key_stats, [3] k_cmp_permute's status
   uint64_t* h_stats = nullptr;    // their four words of the pinned block
-  DevBuf<uint64_t> keys[2];       // the pairs, ping-pong
-  DevBuf<uint32_t> idx[2];
-  DevBuf<uint32_t> hist, totals;
+  RadixPassScratch pass;          // the pairs, ping-pong
   std::vector<DevBuf<uint64_t>> free_vals;  // retired value / NULL buffers: the next
   std::vector<DevBuf<uint8_t>> free_nulls;  // group's destinations
   std::vector<CmpPermuteCol> h_cols;        // (lives until the stream has been synchronised)
@@ -439,31 +438,10 @@ Status sort_rows(Job& j) {
   uint32_t bits = 0;
   for (uint64_t range = sj.st.key_max - sj.st.key_min; range; range >>= 1) ++bits;
   sj.st.passes = (bits + 7) / 8;
-  SortPassArgs a{};
-  a.n = n;
-  a.kmin = sj.st.key_min;
-  a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
-  HIP_TRY(sj.hist.alloc(size_t(256) * a.ntiles * 4));
-  HIP_TRY(sj.totals.alloc(256 * 4));
-  a.hist = sj.hist;
-  a.totals = sj.totals;
-  for (uint32_t p = 0; p < sj.st.passes; ++p) {
-    const uint32_t to = p & 1, from = to ^ 1;
-    if (!sj.keys[to].p) {
-      HIP_TRY(sj.keys[to].alloc(n * 8));
-      HIP_TRY(sj.idx[to].alloc(n * 4));
-    }
-    // the first pass reads the gathered column; its rows are the identity
-    a.keys_in = p ? sj.keys[from].p : j.cols[sj.key].vals.p;
-    a.idx_in = p ? sj.idx[from].p : nullptr;
-    a.keys_out = sj.keys[to];
-    a.idx_out = sj.idx[to];
-    a.shift = 8 * p;
-    HIP_TRY(launch_sort_hist(a, j.s));
-    HIP_TRY(launch_sort_digit_scan(a, j.s));
-    HIP_TRY(launch_sort_scatter(a, j.s));
-    sj.st.n_kernel_launches += 3;
-  }
+  // the first pass reads the gathered column; its rows are the identity
+  Status st = radix_sort_passes(j.cols[sj.key].vals, nullptr, n, sj.st.key_min, sj.st.passes, &sj.pass, j.s);
+  if (!st.ok()) return st;
+  sj.st.n_kernel_launches += 3 * sj.st.passes;
   return Status();
 }
 
@@ -477,8 +455,8 @@ Status permute_columns(Job& j) {
   // buffer are the first destinations
   OutColumn& kc = j.cols[sj.key];
   sj.free_vals.push_back(std::move(kc.vals));
-  kc.vals = std::move(sj.keys[last]);
-  if (sj.keys[last ^ 1].p) sj.free_vals.push_back(std::move(sj.keys[last ^ 1]));
+  kc.vals = std::move(sj.pass.keys[last]);
+  if (sj.pass.keys[last ^ 1].p) sj.free_vals.push_back(std::move(sj.pass.keys[last ^ 1]));
   std::vector<size_t> todo;
   for (size_t c = 0; c < specs.size(); ++c) {
     // (a constant column is the same in every order)
@@ -512,7 +490,7 @@ Status permute_columns(Job& j) {
     HIP_TRY(hipMemcpyAsync(sj.d_cols.p + g, sj.h_cols.data() + g, (ge - g) * sizeof(CmpPermuteCol),
                            hipMemcpyHostToDevice, j.s));
     CmpPermuteArgs a{};
-    a.perm = sj.idx[last];
+    a.perm = sj.pass.idx[last];
     a.n = n;
     a.cols = sj.d_cols.p + g;
     a.ncols = uint32_t(ge - g);

@@ -13,6 +13,7 @@
 // Host waits: one for the heap sizes and the key statistics together (only with a STRING or a
 // sort column), and the writer's.  The query is read, never changed.
 #include <memory>
+#include "radix_sort.h"
 #include "runtime.h"
 
 namespace evql {
@@ -103,25 +104,14 @@ Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int
   ma.rw = r.nwords + 1;
   ma.ncols = ncols;
   ma.status = d_status;
-  DevBuf<uint64_t> d_rows, d_first_vals;
-  DevBuf<uint8_t> d_first_tags;
-  DevBuf<RtColumn> d_rt;
-  std::vector<RtColumn> rc;  // (lives until the stream has been synchronised)
-  const uint32_t nc = uint32_t(kp.cols.size());
+  FirstRows fr;
   if (plan.need_first && n) {
-    st = first_row_columns(q, &rc);
+    // (this route bounds the recorded first rows by the table's rows: the emit routes do not)
+    st = gather_first_rows(q, r.d_rec, n, ma.rw, t->layout.num_rows, d_status, &fr);
     if (!st.ok()) return st;
-    HIP_TRY(d_rows.alloc(n * 8));
-    HIP_TRY(d_rt.alloc(nc * sizeof(RtColumn)));
-    HIP_TRY(d_first_vals.alloc(n * nc * 8));
-    HIP_TRY(d_first_tags.alloc(n * nc));
-    HIP_TRY(launch_mat_first_rows(r.d_rec, n, ma.rw, uint32_t(1 + kp.first_row_word()),
-                                  t->layout.num_rows, d_rows, d_status, s));
-    HIP_TRY(hipMemcpyAsync(d_rt, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_gather_rows(t->d_image, d_rt, nc, d_rows, n, d_first_vals, d_first_tags, s));
     ms.n_kernel_launches += 2;
-    ma.first_vals = d_first_vals;
-    ma.first_tags = d_first_tags;
+    ma.first_vals = fr.vals;
+    ma.first_tags = fr.tags;
   }
   std::vector<OutCol> cols(ncols);
   bool strings = false;
@@ -131,14 +121,7 @@ Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int
     HIP_TRY(oc.vals.alloc(n * 8));
     if (cell.optional) HIP_TRY(oc.nulls.alloc(n));
     MatCol& mc = ma.col[c];
-    mc.kind = cell.kind;
-    mc.word = cell.word;
-    mc.count_word = cell.count_word;
-    mc.is_mean = cell.is_mean;
-    mc.src = cell.src;
-    mc.to_float = cell.to_float;
-    mc.is_string = cell.is_string;
-    mc.is_bool = cell.is_bool;
+    static_cast<ResultCell&>(mc) = cell;
     mc.values = oc.vals;
     mc.nulls = oc.nulls;
     if (cell.is_string) {
@@ -197,8 +180,7 @@ Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int
   HIP_TRY(hipEventRecord(ev.e[3], s));
 
   // ---- 4b. sort, 4c. permute ------------------------------------------------------------------
-  DevBuf<uint64_t> keys[2];
-  DevBuf<uint32_t> idx[2], hist, totals;
+  RadixPassScratch sc;  // (sides and histograms are allocated by the passes that need them)
   DevBuf<CmpPermuteCol> d_pcols;
   std::vector<CmpPermuteCol> h_pcols;  // (lives until the stream has been synchronised)
   std::vector<OutCol> moved(ncols);
@@ -209,35 +191,14 @@ Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int
       uint32_t bits = 0;
       for (uint64_t range = kmax - kmin; range; range >>= 1) ++bits;
       ms.passes = (bits + 7) / 8;
-      SortPassArgs a{};
-      a.n = n;
-      a.kmin = kmin;
-      a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
-      HIP_TRY(hist.alloc(size_t(256) * a.ntiles * 4));
-      HIP_TRY(totals.alloc(256 * 4));
-      a.hist = hist;
-      a.totals = totals;
-      for (uint32_t p = 0; p < ms.passes; ++p) {
-        const uint32_t to = p & 1, from = to ^ 1;
-        if (!keys[to].p) {
-          HIP_TRY(keys[to].alloc(n * 8));
-          HIP_TRY(idx[to].alloc(n * 4));
-        }
-        // the first pass reads the gathered column; its rows are the identity
-        a.keys_in = p ? keys[from].p : cols[sort_column].vals.p;
-        a.idx_in = p ? idx[from].p : nullptr;
-        a.keys_out = keys[to];
-        a.idx_out = idx[to];
-        a.shift = 8 * p;
-        HIP_TRY(launch_sort_hist(a, s));
-        HIP_TRY(launch_sort_digit_scan(a, s));
-        HIP_TRY(launch_sort_scatter(a, s));
-        ms.n_kernel_launches += 3;
-      }
+      // the first pass reads the gathered column; its rows are the identity
+      st = radix_sort_passes(cols[sort_column].vals, nullptr, n, kmin, ms.passes, &sc, s);
+      if (!st.ok()) return st;
+      ms.n_kernel_launches += 3 * ms.passes;
       const uint32_t last = (ms.passes - 1) & 1;
       // the key column's sorted words are the last pass's
       moved[sort_column].vals = std::move(cols[sort_column].vals);
-      cols[sort_column].vals = std::move(keys[last]);
+      cols[sort_column].vals = std::move(sc.keys[last]);
       for (uint32_t c = 0; c < ncols; ++c) {
         if (int(c) == sort_column) continue;
         OutCol& oc = cols[c];
@@ -253,7 +214,7 @@ Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int
         HIP_TRY(hipMemcpyAsync(d_pcols, h_pcols.data(), h_pcols.size() * sizeof(CmpPermuteCol),
                                hipMemcpyHostToDevice, s));
         CmpPermuteArgs pa{};
-        pa.perm = idx[last];
+        pa.perm = sc.idx[last];
         pa.n = n;
         pa.cols = d_pcols;
         pa.ncols = uint32_t(h_pcols.size());

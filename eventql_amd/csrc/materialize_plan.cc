@@ -25,18 +25,6 @@ bool type_fits(uint32_t stype, uint32_t logical) {
   }
 }
 
-// a bare column: `lp` = X_INPUT(j) of the scan select list, whose expression j = X_INPUT(c) of
-// the scan columns
-bool bare_column(const MatInput& in, const LoweredProgram& lp, uint32_t* col) {
-  if (!lp.call || lp.call->kind != Expr::INPUT) return false;
-  const uint32_t j = lp.call->input;
-  if (j >= in.scan_select->size()) return false;
-  const ExprPtr& se = (*in.scan_select)[j].call;
-  if (!se || se->kind != Expr::INPUT) return false;
-  *col = se->input;
-  return *col < in.kp->cols.size();
-}
-
 }  // namespace
 
 int mat_decision_code(MatDecision d) {
@@ -75,6 +63,7 @@ MatDecision plan_materialize(const MatInput& in, MatPlan* out) {
     const MatSpec& sp = specs[i];
     MatCell cell;
     cell.optional = sp.dlevel_max == 1;
+    cell.stype = lp.return_type;
     cell.is_bool = lp.return_type == EVQL_T_BOOL;
     if (lp.return_type == EVQL_T_NIL) {
       return refuse(out, MAT_NIL, "materialise: a NIL-typed column: " + sp.name);
@@ -88,38 +77,27 @@ MatDecision plan_materialize(const MatInput& in, MatPlan* out) {
         return refuse(out, MAT_POST_AGGREGATE, "materialise: post-aggregate arithmetic: " + sp.name);
       }
       const int ai = i < in.select_agg_index->size() ? (*in.select_agg_index)[i] : -1;
-      if (ai < 0 || size_t(ai) >= kp.aggs.size()) {
+      const AggPlan* a = nullptr;
+      if (!aggregate_cell(kp, ai, &cell, &a)) {
         return refuse(out, MAT_POST_AGGREGATE, "materialise: no aggregate state behind: " + sp.name);
       }
-      const AggPlan& a = kp.aggs[ai];
-      if (a.exact_index >= 0) {
+      if (a->exact_index >= 0) {
         return refuse(out, MAT_EXACT_SUM, "materialise: an exact float sum: " + sp.name);
-      }
-      cell.kind = 1;
-      cell.word = uint32_t(1 + kp.state_word_base() + a.first_word);
-      switch (a.fn) {
-        case EVQL_AGG_COUNT: case EVQL_AGG_SUM_UINT64: case EVQL_AGG_SUM_INT64:
-        case EVQL_AGG_SUM_FLOAT64: case EVQL_AGG_COUNT_DISTINCT_UINT64:
-          break;
-        case EVQL_AGG_MEAN_UINT64: case EVQL_AGG_MEAN_INT64: case EVQL_AGG_MEAN_FLOAT64:
-          cell.is_mean = 1;
-          cell.count_word = int32_t(cell.word + 1);
-          break;
-        default:  // min / max
-          cell.count_word = int32_t(cell.word + 1);
       }
     } else if (i < in.select_passthrough->size() && (*in.select_passthrough)[i]) {
       // the exact key: the record's identity word (also after a merge).  A computed key
-      // (`a + 1`) is refused like every other evaluated expression.
+      // (`a + 1`) is refused like every other evaluated expression.  (The key mode must be
+      // EXACT here; FINAL asks for no key mode.)
       uint32_t c = 0;
-      if (kp.key_mode != KEY_EXACT || lp.return_type == EVQL_T_STRING || !bare_column(in, lp, &c)) {
+      if (kp.key_mode != KEY_EXACT || lp.return_type == EVQL_T_STRING ||
+          !bare_column(kp, *in.scan_select, lp, &c)) {
         return refuse(out, MAT_KEY_EXPR, "materialise: a computed key: " + sp.name);
       }
       cell.kind = 0;
     } else {
       // a bare column read from the group's first row (the columns of a hashed key among them)
       uint32_t c = 0;
-      if (!bare_column(in, lp, &c) || !kp.need_first_row) {
+      if (!bare_column(kp, *in.scan_select, lp, &c) || !kp.need_first_row) {
         return refuse(out, MAT_KEY_EXPR, "materialise: a computed or hashed key or select expression "
                                          "that is not a first-row bare column: " + sp.name);
       }
@@ -127,14 +105,11 @@ MatDecision plan_materialize(const MatInput& in, MatPlan* out) {
         return refuse(out, MAT_FIRST_ROW, std::string("materialise: a first-row column of a ") +
                                               (in.merged ? "merged result: " : "nested scan: ") + sp.name);
       }
-      const ColAccess& ca = kp.cols[c];
-      if (ca.stype != lp.return_type || (lp.return_type == EVQL_T_STRING) != ca.string_hash) {
+      // (a STRING only from a hashed string column: FINAL does not ask)
+      if (!first_row_cell(kp, *in.scan_select, lp, &cell) ||
+          (lp.return_type == EVQL_T_STRING) != bool(cell.is_string)) {
         return refuse(out, MAT_KEY_EXPR, "materialise: the column's type is not the expression's: " + sp.name);
       }
-      cell.kind = 2;
-      cell.src = c;
-      cell.to_float = ca.stype == EVQL_T_FLOAT64 && ca.from_uint_to_float;
-      cell.is_string = ca.string_hash;
       out->need_first = true;
     }
     if (!type_fits(lp.return_type, sp.logical_type)) {

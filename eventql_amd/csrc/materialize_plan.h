@@ -6,23 +6,13 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "result_cell.h"
 
 namespace evql {
 
-struct KernelPlan;
-struct LoweredProgram;
-
-// one output column, as the k_mat_* kernels read it (aot_kernels.h MatCol is filled from it)
-struct MatCell {
-  uint32_t kind = 0;       // 0 the exact key (record word 1; NULL when the kind word is 2),
-                           // 1 an aggregate's state, 2 scan column `src` at the group's first row
-  uint32_t word = 0;       // kind 1: record word of the state
-  int32_t count_word = -1; // kind 1, min / max / mean: record word of the non-NULL count
-  uint32_t is_mean = 0;    // kind 1: value = float sum / double(count)
-  uint32_t src = 0;        // kind 2: scan column index
-  uint32_t to_float = 0;   // kind 2: (double) of the unsigned raw value
-  uint32_t is_string = 0;  // kind 2: the value word is (len << 40 | position) in the column's pages
-  uint32_t is_bool = 0;    // the value word is 0 | 1
+// one output column: where the k_mat_* kernels read it (result_cell.h; aot_kernels.h MatCol
+// takes the cell as it is) and what only the host needs to know
+struct MatCell : ResultCell {
   uint32_t optional = 0;   // the spec's dlevel_max == 1: the column takes NULL bytes
 };
 

@@ -12,6 +12,7 @@
 // last row of a group carries the non-aggregate values (groupby.cc:606-610).  The result has
 // the layout of its input, so it is the next fold's first part.
 #include "merge_device.h"
+#include "radix_sort.h"
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -113,39 +114,23 @@ Status stage_for(MergeDevice* d, size_t bytes) {
   return Status();
 }
 
-struct SortScratch {
-  DevBuf<uint64_t> keys[2];
-  DevBuf<uint32_t> idx[2];
-  DevBuf<uint32_t> hist, totals;
-  uint32_t cur = 0;
+// Side 1 of the ping-pong holds the current order: every sort here runs an even number of
+// passes, so it ends where it began.
+struct SortScratch : RadixPassScratch {
   bool have_perm = false;
 };
 
 // a stable sort of the current order (the identity at first) by the low `bits` bits of record
-// word `word`: chain_compact.cc sort_rows, over gathered key words
+// word `word`: the digit passes over gathered key words, kmin 0, no statistics
 Status sort_by_word(MergeDevice* d, SortScratch* S, uint64_t n, uint32_t word, uint32_t bits) {
-  HIP_TRY(launch_mrg_gather_key(d->rec, d->L.rw, word, S->have_perm ? S->idx[S->cur].p : nullptr, n,
-                                S->keys[S->cur], d->s));
-  SortPassArgs a{};
-  a.n = n;
-  a.kmin = 0;
-  a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
-  a.hist = S->hist;
-  a.totals = S->totals;
-  for (uint32_t p = 0; p < bits / 8; ++p) {
-    const uint32_t from = S->cur, to = from ^ 1;
-    a.keys_in = S->keys[from];
-    a.idx_in = S->have_perm ? S->idx[from].p : nullptr;
-    a.keys_out = S->keys[to];
-    a.idx_out = S->idx[to];
-    a.shift = 8 * p;
-    HIP_TRY(launch_sort_hist(a, d->s));
-    HIP_TRY(launch_sort_digit_scan(a, d->s));
-    HIP_TRY(launch_sort_scatter(a, d->s));
-    S->cur = to;
-    S->have_perm = true;
-    ++d->st.sort_passes;
-  }
+  const uint32_t passes = bits / 8;
+  if (passes & 1) return Status::error(EVQL_ERUNTIME, "merge: an odd number of sort passes");
+  const uint32_t* perm = S->have_perm ? S->idx[1].p : nullptr;
+  HIP_TRY(launch_mrg_gather_key(d->rec, d->L.rw, word, perm, n, S->keys[1], d->s));
+  Status st = radix_sort_passes(S->keys[1], perm, n, 0, passes, S, d->s);
+  if (!st.ok()) return st;
+  S->have_perm = S->have_perm || passes > 0;
+  d->st.sort_passes += passes;
   return Status();
 }
 
@@ -180,7 +165,7 @@ Status compact(MergeDevice* d) {
     if (st.ok()) st = sort_by_word(d, &S, n, 0, 64);
     if (!st.ok()) return st;
     HIP_TRY(hipMemsetAsync(counters.p, 0, 8, d->s));
-    HIP_TRY(launch_mrg_heads(d->rec, rw, S.idx[S.cur], n, flags, heads, counters, d->s));
+    HIP_TRY(launch_mrg_heads(d->rec, rw, S.idx[1], n, flags, heads, counters, d->s));
     HIP_TRY(launch_exclusive_scan(heads, n, heads.p + n, d->s));
     HIP_TRY(hipMemcpyAsync(&h_collisions, counters.p, 8, hipMemcpyDeviceToHost, d->s));
     HIP_TRY(hipMemcpyAsync(&h_groups, heads.p + n, 8, hipMemcpyDeviceToHost, d->s));
@@ -195,7 +180,7 @@ Status compact(MergeDevice* d) {
   MrgFoldArgs fa{};
   fa.L = d->L;
   fa.records = d->rec;
-  fa.perm = S.idx[S.cur];
+  fa.perm = S.idx[1];
   fa.flags = flags;
   fa.seg = heads;
   fa.n = n;
@@ -333,7 +318,6 @@ Status pack_on_device(MergeDevice* d) {
   std::vector<DevBuf<uint8_t>> d_out(nsel);
   std::vector<DevBuf<uint64_t>> d_aux(nsel);
   std::unique_ptr<EmitArgs> ea(new EmitArgs());
-  memset(ea.get(), 0, sizeof(EmitArgs));
   ea->records = d->rec;
   ea->n = n;
   ea->rw = d->L.rw;
@@ -342,8 +326,8 @@ Status pack_on_device(MergeDevice* d) {
   for (size_t i = 0; i < nsel; ++i) {
     const LoweredProgram& lp = d->select[i];
     EmitCol& e = ea->col[i];
-    e.count_word = -1;
     if (!bare_aggregate(lp)) continue;  // (elem 0: k_emit_fixed leaves the column alone)
+    // a state cell by the merge record's own layout (merge_frame_index.h), not the plan's
     e.kind = 1;
     e.stype = lp.return_type;
     e.word = d->L.word[i];

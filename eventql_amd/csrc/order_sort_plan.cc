@@ -8,43 +8,35 @@ namespace evql {
 OrderKeyClass classify_order_key(const KernelPlan& kp, const std::vector<LoweredProgram>& select,
                                  const std::vector<int>& select_agg_index,
                                  const std::vector<bool>& select_passthrough,
-                                 const LoweredProgram& spec, bool descending, OrderKeySpec* out) {
+                                 const LoweredProgram& spec, bool descending, OrderKeyArgs* out) {
   if (!spec.call || spec.call->kind != Expr::INPUT) return OKEY_EXPRESSION;
   const uint32_t si = spec.call->input;
   if (si >= select.size()) return OKEY_UNREADABLE;
   const LoweredProgram& sp = select[si];
   auto type_code = [](uint32_t t) { return t == EVQL_T_INT64 ? 1u : (t == EVQL_T_FLOAT64 ? 2u : 0u); };
-  OrderKeySpec ok{};
-  ok.count_word = -1;
+  OrderKeyArgs ok{};
+  ok.stype = sp.return_type;
   ok.descending = descending;
   if (si < select_passthrough.size() && select_passthrough[si] && sp.return_type != EVQL_T_STRING) {
+    // (no key-mode rule: a hashed key's identity orders as the host orders it)
+    ok.kind = 0;
     ok.from_ident = 1;
     ok.word = 1;
     ok.type = type_code(sp.return_type);
   } else if (sp.is_aggregate && sp.call && sp.call->kind == Expr::AGG_GET) {
     const int ai = si < select_agg_index.size() ? select_agg_index[si] : -1;
-    if (ai < 0 || size_t(ai) >= kp.aggs.size()) return OKEY_UNREADABLE;
-    const AggPlan& a = kp.aggs[ai];
-    ok.word = uint32_t(1 + kp.state_word_base() + a.first_word);
-    switch (a.fn) {
-      case EVQL_AGG_COUNT:
-      case EVQL_AGG_COUNT_DISTINCT_UINT64:  // (one word: the number of distinct values)
-      case EVQL_AGG_SUM_UINT64: ok.type = 0; break;
-      case EVQL_AGG_SUM_INT64: ok.type = 1; break;
-      case EVQL_AGG_SUM_FLOAT64:
-        if (a.exact_index >= 0) return OKEY_EXACT_SUM;
-        ok.type = 2;
-        break;
-      case EVQL_AGG_MEAN_UINT64:
-      case EVQL_AGG_MEAN_INT64:
-      case EVQL_AGG_MEAN_FLOAT64:
-        ok.type = 2;
-        ok.is_mean = 1;
-        ok.count_word = int32_t(ok.word + 1);
-        break;
-      default:  // min / max
-        ok.type = type_code(sp.return_type);
-        ok.count_word = int32_t(ok.word + 1);
+    const AggPlan* a = nullptr;
+    if (!aggregate_cell(kp, ai, &ok, &a)) return OKEY_UNREADABLE;
+    // how the state orders: the function's own type, not the expression's, except for min / max
+    if (a->fn == EVQL_AGG_SUM_FLOAT64) {
+      if (a->exact_index >= 0) return OKEY_EXACT_SUM;
+      ok.type = 2;
+    } else if (a->fn == EVQL_AGG_SUM_INT64) {
+      ok.type = 1;
+    } else if (ok.is_mean) {
+      ok.type = 2;
+    } else {  // min / max by the expression's type; the counts are unsigned
+      ok.type = ok.count_word >= 0 ? type_code(sp.return_type) : 0u;
     }
   } else {
     return OKEY_UNREADABLE;
@@ -63,7 +55,7 @@ OrderSortDecision plan_order_sort(const OrderSortInput& in, OrderSortPlan* out) 
   if (in.n >= (1ull << 32)) return OSORT_TOO_MANY_RECORDS;
   const KernelPlan& kp = *in.kp;
   for (size_t j = 0; j < ns; ++j) {
-    OrderKeySpec ok{};
+    OrderKeyArgs ok{};
     const bool desc = j < in.order_desc->size() && (*in.order_desc)[j];
     switch (classify_order_key(kp, *in.select, *in.select_agg_index, *in.select_passthrough,
                                (*in.order)[j], desc, &ok)) {

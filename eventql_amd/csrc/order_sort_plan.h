@@ -5,23 +5,24 @@
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "result_cell.h"
 
 namespace evql {
 
-struct KernelPlan;
-struct LoweredProgram;
-
 static const uint32_t kMaxOrderSortSpecs = 8;
 
-// where the device finds one sort key in a record: the host-side fields of OrderKeyArgs
-// (aot_kernels.h)
-struct OrderKeySpec {
-  uint32_t from_ident;  // 1: the group key itself (record[0] = kind, record[1] = identity)
-  uint32_t word;        // record word holding the value (state word / identity)
-  int32_t count_word;   // >= 0: non-null input count (min / max / mean); 0 => value reads 0
-  uint32_t type;        // 0 unsigned, 1 signed, 2 float64
-  uint32_t is_mean;     // value = f64(word) / count
-  uint32_t descending;
+// The 64-bit order-preserving key of one sort expression, per dense record: where the device
+// finds the value in a record (result_cell.h: the key, kind 0 with word 1, or a state, kind 1;
+// a NULL reads 0) and how it orders.  The plan fills the cell, type, descending and from_ident;
+// the runtime adds the pointers and counts (k_order_keys, k_ord_key_perm: aot_kernels.h).
+struct OrderKeyArgs : ResultCell {
+  const uint64_t* records = nullptr;  // [n][record_words]
+  uint32_t record_words = 0;
+  uint64_t n = 0;
+  uint32_t from_ident = 0;  // 1: the group key itself (record[0] = kind, record[1] = identity)
+  uint32_t type = 0;        // 0 unsigned, 1 signed, 2 float64 (cmp_uint64 / _int64 / _float64)
+  uint32_t descending = 0;
+  uint64_t* keys = nullptr;
 };
 
 // one sort expression against the select list
@@ -57,7 +58,7 @@ struct OrderSortInput {
 };
 
 struct OrderSortPlan {
-  std::vector<OrderKeySpec> keys;  // one per sort spec, in spec order
+  std::vector<OrderKeyArgs> keys;  // one per sort spec, in spec order
   uint32_t base_word = 1;          // the record word sort_host_records orders by
 };
 
@@ -66,7 +67,7 @@ struct OrderSortPlan {
 OrderKeyClass classify_order_key(const KernelPlan& kp, const std::vector<LoweredProgram>& select,
                                  const std::vector<int>& select_agg_index,
                                  const std::vector<bool>& select_passthrough,
-                                 const LoweredProgram& spec, bool descending, OrderKeySpec* out);
+                                 const LoweredProgram& spec, bool descending, OrderKeyArgs* out);
 
 // The rules of DESIGN.md 3.13.  Returns OSORT_DEVICE and fills *out, or why order_fetched
 // keeps the result.

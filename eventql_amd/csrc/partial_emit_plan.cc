@@ -6,34 +6,19 @@ namespace evql {
 
 namespace {
 
-// a bare column: `lp` = X_INPUT(j) of the scan select list, whose expression j = X_INPUT(c) of
-// the scan columns
-bool bare_column(const PartialEmitInput& in, const LoweredProgram& lp, uint32_t* col) {
-  if (!lp.call || lp.call->kind != Expr::INPUT) return false;
-  const uint32_t j = lp.call->input;
-  if (j >= in.scan_select->size()) return false;
-  const ExprPtr& se = (*in.scan_select)[j].call;
-  if (!se || se->kind != Expr::INPUT) return false;
-  *col = se->input;
-  return *col < in.kp->cols.size();
+// the exact key: the record's identity word (also after a merge)
+void key_cell(const LoweredProgram& lp, PartialCell* cell) {
+  cell->kind = 0;
+  cell->stype = lp.return_type;
+  cell->is_bool = lp.return_type == EVQL_T_BOOL;
 }
 
-// ... read from the group's first row: what device_emit_columns (results.cc) accepts as kind 2
-bool first_row_cell(const PartialEmitInput& in, const LoweredProgram& lp, PartialCell* cell) {
-  const KernelPlan& kp = *in.kp;
-  if (in.merged || !kp.need_first_row) return false;
-  uint32_t c = 0;
-  if (!bare_column(in, lp, &c)) return false;
-  const ColAccess& ca = kp.cols[c];
-  if (ca.stype != lp.return_type) return false;
-  if ((lp.return_type == EVQL_T_STRING) != ca.string_hash) return false;
-  cell->kind = 2;
-  cell->stype = lp.return_type;
-  cell->src = c;
-  cell->to_float = ca.stype == EVQL_T_FLOAT64 && ca.from_uint_to_float;
-  cell->is_string = ca.string_hash;
-  cell->is_bool = lp.return_type == EVQL_T_BOOL;
-  return true;
+// a first-row cell as PARTIAL takes it: never of a merged result, a STRING only from a hashed
+// string column
+bool partial_first_row_cell(const PartialEmitInput& in, const LoweredProgram& lp, PartialCell* cell) {
+  if (in.merged || !in.kp->need_first_row) return false;
+  if (!first_row_cell(*in.kp, *in.scan_select, lp, cell)) return false;
+  return (lp.return_type == EVQL_T_STRING) == bool(cell->is_string);
 }
 
 }  // namespace
@@ -53,16 +38,14 @@ PartialEmitDecision plan_partial_emit(const PartialEmitInput& in, PartialEmitPla
     PartialCell cell{};
     if (lp.return_type == EVQL_T_NIL) return PEMIT_NIL_COLUMN;
     if (kp.key_mode == KEY_EXACT) {
-      // one fixed-width key, a bare column: the record's identity word (also after a merge).
-      // A computed key (`a + 1`) keeps the host loop like every other evaluated expression.
+      // one fixed-width key, a bare column.  A computed key (`a + 1`) keeps the host loop like
+      // every other evaluated expression.
       uint32_t c = 0;
-      if (ngroup != 1 || lp.return_type == EVQL_T_STRING || !bare_column(in, lp, &c)) {
+      if (ngroup != 1 || lp.return_type == EVQL_T_STRING || !bare_column(kp, *in.scan_select, lp, &c)) {
         return PEMIT_GROUP_EXPR;
       }
-      cell.kind = 0;
-      cell.stype = lp.return_type;
-      cell.is_bool = lp.return_type == EVQL_T_BOOL;
-    } else if (kp.key_mode != KEY_HASHED || !first_row_cell(in, lp, &cell)) {
+      key_cell(lp, &cell);
+    } else if (kp.key_mode != KEY_HASHED || !partial_first_row_cell(in, lp, &cell)) {
       return PEMIT_GROUP_EXPR;
     }
     out->tuple.push_back(cell);
@@ -71,18 +54,16 @@ PartialEmitDecision plan_partial_emit(const PartialEmitInput& in, PartialEmitPla
     const LoweredProgram& lp = (*in.select)[i];
     PartialCell cell{};
     if (lp.is_aggregate) {
-      // (PARTIAL rows carry the saved state, whatever the expression does with the value)
-      const int ai = (*in.select_agg_index)[i];
-      if (ai < 0 || size_t(ai) >= kp.aggs.size()) return PEMIT_AGGREGATE;
-      const AggPlan& a = kp.aggs[ai];
-      cell.kind = 1;
-      cell.word = uint32_t(1 + kp.state_word_base() + a.first_word);
-      switch (a.fn) {
+      // PARTIAL rows carry the saved state, whatever the expression does with the value: no
+      // AGG_GET rule here, unlike the FINAL routes
+      const AggPlan* a = nullptr;
+      if (!aggregate_cell(kp, (*in.select_agg_index)[i], &cell, &a)) return PEMIT_AGGREGATE;
+      switch (a->fn) {
         case EVQL_AGG_COUNT: case EVQL_AGG_SUM_UINT64: case EVQL_AGG_SUM_INT64:
           cell.state = PSTATE_VARUINT;
           break;
         case EVQL_AGG_SUM_FLOAT64:
-          if (a.exact_index >= 0) return PEMIT_AGGREGATE;  // (128-bit rounding: host)
+          if (a->exact_index >= 0) return PEMIT_AGGREGATE;  // (128-bit rounding: host)
           cell.state = PSTATE_RAW8;
           break;
         case EVQL_AGG_MIN_UINT64: case EVQL_AGG_MAX_UINT64: case EVQL_AGG_MIN_INT64:
@@ -96,11 +77,10 @@ PartialEmitDecision plan_partial_emit(const PartialEmitInput& in, PartialEmitPla
     } else {
       if (lp.return_type == EVQL_T_NIL) return PEMIT_NIL_COLUMN;
       if (i < in.select_passthrough->size() && (*in.select_passthrough)[i]) {
+        // (the key mode must be EXACT here; FINAL asks for no key mode)
         if (kp.key_mode != KEY_EXACT || lp.return_type == EVQL_T_STRING) return PEMIT_SELECT_EXPR;
-        cell.kind = 0;
-        cell.stype = lp.return_type;
-        cell.is_bool = lp.return_type == EVQL_T_BOOL;
-      } else if (!first_row_cell(in, lp, &cell)) {
+        key_cell(lp, &cell);
+      } else if (!partial_first_row_cell(in, lp, &cell)) {
         return PEMIT_SELECT_EXPR;
       }
     }

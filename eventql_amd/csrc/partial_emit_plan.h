@@ -5,28 +5,19 @@
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "result_cell.h"
 
 namespace evql {
-
-struct KernelPlan;
-struct LoweredProgram;
 
 // results of at least this many groups are packed on the device (FINAL and PARTIAL)
 static const uint64_t kDeviceEmitMinGroups = 1 << 16;
 static const uint32_t kMaxEmitCols = 32;
 
-// one cell of a PARTIAL row, as the k_partial_* kernels read it
-struct PartialCell {
-  uint32_t kind;      // 0 the exact key (record word 1; NULL when the kind word is 2),
-                      // 1 an aggregate's saved state, 2 scan column `src` at the group's first row
-  uint32_t stype;     // evql_stype of the value (kind 0 / 2)
-  uint32_t word;      // kind 1: record word of the state; the non-NULL count is word + 1
-  uint32_t state;     // kind 1: PartialState
-  uint32_t src;       // kind 2: scan column index
-  uint32_t to_float;  // kind 2: (double) of the unsigned raw value
-  uint32_t is_string; // kind 2: the value word is (len << 40 | position) in the column's pages
-  uint32_t is_bool;   // kind 0 / 2: a BOOL element (value byte, tag byte)
-  const uint64_t* pages;  // strings: data pages of the source column (set by the runtime)
+// one cell of a PARTIAL row, as the k_partial_* kernels read it: where it lives (result_cell.h)
+// and what a PARTIAL row adds
+struct PartialCell : ResultCell {
+  uint32_t state = 0;     // kind 1: PartialState
+  const uint64_t* pages = nullptr;  // strings: data pages of the source column (set by the runtime)
 };
 enum PartialState {
   PSTATE_VARUINT = 0,       // count / integer sum: LEB128 of the word

@@ -4,12 +4,39 @@
 
 namespace evql {
 
+Status radix_sort_passes(const uint64_t* keys_in, const uint32_t* idx_in, uint64_t n, uint64_t kmin,
+                         uint32_t passes, RadixPassScratch* sc, hipStream_t s) {
+  if (passes == 0) return Status();
+  SortPassArgs a{};
+  a.n = n;
+  a.kmin = kmin;
+  a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
+  if (!sc->hist.p) HIP_TRY(sc->hist.alloc(size_t(256) * a.ntiles * 4));
+  if (!sc->totals.p) HIP_TRY(sc->totals.alloc(256 * 4));
+  a.hist = sc->hist;
+  a.totals = sc->totals;
+  for (uint32_t p = 0; p < passes; ++p) {
+    const uint32_t to = p & 1, from = to ^ 1;
+    if (!sc->keys[to].p) HIP_TRY(sc->keys[to].alloc(n * 8));
+    if (!sc->idx[to].p) HIP_TRY(sc->idx[to].alloc(n * 4));
+    a.keys_in = p ? sc->keys[from].p : keys_in;
+    a.idx_in = p ? sc->idx[from].p : idx_in;
+    a.keys_out = sc->keys[to];
+    a.idx_out = sc->idx[to];
+    a.shift = 8 * p;
+    HIP_TRY(launch_sort_hist(a, s));
+    HIP_TRY(launch_sort_digit_scan(a, s));
+    HIP_TRY(launch_sort_scatter(a, s));
+  }
+  return Status();
+}
+
 Status RadixSortScratch::alloc(uint64_t n) {
   const uint64_t ntiles = (n + kSortTile - 1) / kSortTile;
-  HIP_TRY(keys_alt.alloc(n * 8));
-  HIP_TRY(idx_alt.alloc(n * 4));
-  HIP_TRY(hist.alloc(size_t(256) * ntiles * 4));
-  HIP_TRY(totals.alloc(256 * 4));
+  HIP_TRY(pass.keys[0].alloc(n * 8));
+  HIP_TRY(pass.idx[0].alloc(n * 4));
+  HIP_TRY(pass.hist.alloc(size_t(256) * ntiles * 4));
+  HIP_TRY(pass.totals.alloc(256 * 4));
   HIP_TRY(stats.alloc(4 * 8));
   return Status();
 }
@@ -32,26 +59,21 @@ Status radix_sort_pairs(DevBuf<uint64_t>* keys, DevBuf<uint32_t>* idx, uint64_t 
   uint32_t bits = 0;
   for (uint64_t range = kmax - kmin; range; range >>= 1) ++bits;
   const uint32_t passes = (bits + 7) / 8;
-  SortPassArgs a{};
-  a.n = n;
-  a.kmin = kmin;
-  a.ntiles = uint32_t((n + kSortTile - 1) / kSortTile);
-  a.hist = sc->hist;
-  a.totals = sc->totals;
-  for (uint32_t p = 0; p < passes; ++p) {
-    a.keys_in = *keys;
-    a.idx_in = sc->idx_identity ? nullptr : idx->p;
-    a.keys_out = sc->keys_alt;
-    a.idx_out = sc->idx_alt;
-    a.shift = 8 * p;
-    HIP_TRY(launch_sort_hist(a, s));
-    HIP_TRY(launch_sort_digit_scan(a, s));
-    HIP_TRY(launch_sort_scatter(a, s));
-    sc->launches += 3;
-    std::swap(*keys, sc->keys_alt);
-    std::swap(*idx, sc->idx_alt);
-    sc->idx_identity = false;
+  // the caller's pair is side 1 of the ping-pong, the scratch's side 0
+  RadixPassScratch& pp = sc->pass;
+  pp.keys[1] = std::move(*keys);
+  pp.idx[1] = std::move(*idx);
+  Status st = radix_sort_passes(pp.keys[1], sc->idx_identity ? nullptr : pp.idx[1].p, n, kmin, passes, &pp, s);
+  const uint32_t last = (passes - 1) & 1;
+  if (last == 0) {
+    std::swap(pp.keys[0], pp.keys[1]);
+    std::swap(pp.idx[0], pp.idx[1]);
   }
+  *keys = std::move(pp.keys[1]);
+  *idx = std::move(pp.idx[1]);
+  if (!st.ok()) return st;
+  sc->launches += 3 * passes;
+  sc->idx_identity = false;
   *passes_run += passes;
   *passes_skipped += 8 - passes;
   return Status();

@@ -1,16 +1,32 @@
-// radix_sort.h -- one driver for the stable LSD radix sort of (u64 key, u32 index) pairs
-// (launch_sort_hist / _digit_scan / _scatter, aot_kernels.h): key statistics first, then only
-// the digit passes the keys need.
+// radix_sort.h -- the one driver of the stable LSD radix sort of (u64 key, u32 index) pairs
+// (launch_sort_hist / _digit_scan / _scatter, aot_kernels.h): the digit passes, which every
+// sort on the device runs through (results.cc sort_on_device, materialize.cc, chain_compact.cc
+// sort_rows, merge_device.cc sort_by_word), and -- for callers whose statistics ride on no
+// other wait -- the key statistics in front of them.
 #pragma once
 #include "runtime.h"
 
 namespace evql {
 
+// the two sides of the ping-pong: pass p writes side p & 1 and -- behind pass 0 -- reads the
+// other one
+struct RadixPassScratch {
+  DevBuf<uint64_t> keys[2];  // n each
+  DevBuf<uint32_t> idx[2];   // n each
+  DevBuf<uint32_t> hist;     // [256][ceil(n / kSortTile)]
+  DevBuf<uint32_t> totals;   // [256]
+};
+
+// `passes` digit passes of 8 bits, from bit 0 of key - kmin upwards: three launches each, no
+// wait.  Pass 0 reads keys_in and idx_in (NULL: the identity 0 .. n-1), which may be side 1 of
+// the scratch itself.  What the passes need and the scratch does not hold yet is allocated
+// here: no pass, no allocation; one pass, side 0 alone.  The sorted pairs are in side
+// (passes - 1) & 1.  n < 2^32.
+Status radix_sort_passes(const uint64_t* keys_in, const uint32_t* idx_in, uint64_t n, uint64_t kmin,
+                         uint32_t passes, RadixPassScratch* scratch, hipStream_t s);
+
 struct RadixSortScratch {
-  DevBuf<uint64_t> keys_alt;  // n: the other side of the ping-pong
-  DevBuf<uint32_t> idx_alt;   // n
-  DevBuf<uint32_t> hist;      // [256][ceil(n / kSortTile)]
-  DevBuf<uint32_t> totals;    // [256]
+  RadixPassScratch pass;
   // [0..2] launch_sort_key_stats, zeroed by every sort; [3] the caller's: a status word its
   // own kernels raise, copied to the host with the statistics in the sort's one wait
   DevBuf<uint64_t> stats;

@@ -63,50 +63,32 @@ static bool device_emit_columns(const evql_query* q, bool merged, EmitArgs* ea, 
     const LoweredProgram& lp = q->select[i];
     EmitCol& e = ea->col[i];
     e = EmitCol{};
-    e.count_word = -1;
     e.stype = lp.return_type;
-    e.elem = lp.return_type == EVQL_T_BOOL ? 2 : 9;
+    e.is_bool = lp.return_type == EVQL_T_BOOL;
+    e.elem = e.is_bool ? 2 : 9;
     if (lp.return_type == EVQL_T_NIL) return false;
     if (lp.is_aggregate) {
       if (lp.call->kind != Expr::AGG_GET) return false;  // post-aggregate arithmetic: host
-      const AggPlan& a = kp.aggs[q->select_agg_index[i]];
-      if (a.exact_index >= 0) return false;  // (128-bit rounding of an exact sum: host)
-      e.kind = 1;
-      e.word = uint32_t(1 + kp.state_word_base() + a.first_word);
-      switch (a.fn) {
-        case EVQL_AGG_COUNT: case EVQL_AGG_SUM_UINT64: case EVQL_AGG_SUM_INT64:
-        case EVQL_AGG_SUM_FLOAT64: case EVQL_AGG_COUNT_DISTINCT_UINT64:
-          break;
-        case EVQL_AGG_MEAN_UINT64: case EVQL_AGG_MEAN_INT64: case EVQL_AGG_MEAN_FLOAT64:
-          e.is_mean = 1;
-          e.count_word = int32_t(e.word + 1);
-          break;
-        default:  // min / max
-          e.count_word = int32_t(e.word + 1);
-      }
+      const AggPlan* a = nullptr;
+      if (!aggregate_cell(kp, q->select_agg_index[i], &e, &a)) return false;
+      if (a->exact_index >= 0) return false;  // (128-bit rounding of an exact sum: host)
     } else if (q->select_passthrough[i]) {
+      // (any key mode, and no bare-column rule: the other routes ask for both)
       if (lp.return_type == EVQL_T_STRING) return false;
       e.kind = 0;
     } else {
-      // a bare column: select expr = X_INPUT(j) of the scan select list = X_INPUT(c)
-      if (merged || !kp.need_first_row || lp.call->kind != Expr::INPUT) return false;
-      const uint32_t j = lp.call->input;
-      if (j >= q->scan_select.size() || q->scan_select[j].call->kind != Expr::INPUT) return false;
-      const uint32_t c = q->scan_select[j].call->input;
-      if (c >= kp.cols.size() || q->nested) return false;
-      const ColAccess& ca = kp.cols[c];
-      if (ca.stype != lp.return_type) return false;
-      e.kind = 2;
-      e.src = c;
-      e.to_float = ca.stype == EVQL_T_FLOAT64 && ca.from_uint_to_float;
-      if (ca.string_hash) e.elem = 0;
+      if (merged || !kp.need_first_row || q->nested) return false;
+      // (a string column is taken by string_hash alone; the other routes also ask that the
+      // expression's type is STRING)
+      if (!first_row_cell(kp, q->scan_select, lp, &e)) return false;
+      if (e.is_string) e.elem = 0;
     }
   }
   ea->ncols = uint32_t(nsel);
   return true;
 }
 
-static Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes) {
+Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes) {
   if (bytes <= *cap && *p) return Status();
   if (*p) hipHostFree(*p);
   *p = nullptr;
@@ -117,112 +99,147 @@ static Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes) {
   return Status();
 }
 
+Status gather_first_rows(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t rw,
+                         uint64_t row_limit, uint64_t* d_status, FirstRows* fr) {
+  const KernelPlan& kp = q->rplan();
+  hipStream_t s = q->ctx->stream;
+  const uint32_t nc = uint32_t(kp.cols.size());
+  Status st = first_row_columns(q, &fr->host_cols);
+  if (!st.ok()) return st;
+  if (d_rec) HIP_TRY(fr->rows.alloc(n * 8));
+  HIP_TRY(fr->cols.alloc(nc * sizeof(RtColumn)));
+  HIP_TRY(fr->vals.alloc(n * nc * 8));
+  HIP_TRY(fr->tags.alloc(n * nc));
+  const uint32_t word = uint32_t(1 + kp.first_row_word());
+  if (d_rec && row_limit != kNoRowLimit) {
+    HIP_TRY(launch_mat_first_rows(d_rec, n, rw, word, row_limit, fr->rows, d_status, s));
+  } else if (d_rec) {
+    HIP_TRY(launch_extract_word(d_rec, n, rw, word, fr->rows, s));
+  }
+  HIP_TRY(hipMemcpyAsync(fr->cols, fr->host_cols.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_gather_rows(q->table->d_image, fr->cols, nc, fr->rows, n, fr->vals, fr->tags, s));
+  return Status();
+}
+
+Status emit_columns_begin(evql_query* q, EmitArgs* ea, EmitColumnsJob* job) {
+  hipStream_t s = q->ctx->stream;
+  const uint32_t ncols = ea->ncols;
+  const uint64_t n = ea->n;
+  evql_query::DeviceEmit& de = q->demit;
+  de.col.resize(ncols, nullptr);
+  de.col_cap.resize(ncols, 0);
+  de.off.resize(ncols, nullptr);
+  de.off_cap.resize(ncols, 0);
+  de.elem.assign(ncols, 0);
+  // device buffers of the packed columns
+  job->d_out = std::vector<DevBuf<uint8_t>>(ncols);
+  job->d_off = std::vector<DevBuf<uint64_t>>(ncols);
+  job->str_bytes.assign(ncols, 0);
+  HIP_TRY(job->d_args.alloc(sizeof(EmitArgs)));
+  for (uint32_t i = 0; i < ncols; ++i) {
+    EmitCol& e = ea->col[i];
+    de.elem[i] = e.elem;
+    if (e.elem) {
+      HIP_TRY(job->d_out[i].alloc(n * e.elem));
+      e.out = job->d_out[i];
+    } else {
+      HIP_TRY(job->d_off[i].alloc((n + 2) * 8));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(job->d_args, ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_emit_fixed(job->d_args, n, s));
+  ++job->launches;
+  for (uint32_t i = 0; i < ncols; ++i) {
+    if (ea->col[i].elem) continue;
+    HIP_TRY(launch_emit_str_sizes(job->d_args, i, n, job->d_off[i], s));
+    HIP_TRY(launch_exclusive_scan(job->d_off[i], n, job->d_off[i].p + n, s));
+    HIP_TRY(hipMemcpyAsync(&job->str_bytes[i], job->d_off[i].p + n, 8, hipMemcpyDeviceToHost, s));
+    job->launches += 2;
+  }
+  return Status();
+}
+
+Status emit_columns_finish(evql_query* q, EmitArgs* ea, EmitColumnsJob* job) {
+  hipStream_t s = q->ctx->stream;
+  const uint32_t ncols = ea->ncols;
+  const uint64_t n = ea->n;
+  evql_query::DeviceEmit& de = q->demit;
+  bool strings = false;
+  for (uint32_t i = 0; i < ncols; ++i) {
+    if (ea->col[i].elem) continue;
+    strings = true;
+    HIP_TRY(job->d_out[i].alloc(job->str_bytes[i] + 16));
+    ea->col[i].out = job->d_out[i];
+    ea->col[i].offsets = job->d_off[i];
+  }
+  if (strings) {
+    HIP_TRY(hipMemcpyAsync(job->d_args, ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
+    for (uint32_t i = 0; i < ncols; ++i) {
+      if (ea->col[i].elem) continue;
+      HIP_TRY(launch_emit_str_bytes(job->d_args, i, n, s));
+      ++job->launches;
+    }
+  }
+  // one copy per column into pinned host memory
+  for (uint32_t i = 0; i < ncols; ++i) {
+    const size_t bytes = ea->col[i].elem ? size_t(n) * ea->col[i].elem : size_t(job->str_bytes[i]);
+    Status st = pinned_reserve(&de.col[i], &de.col_cap[i], bytes);
+    if (!st.ok()) return st;
+    if (bytes) HIP_TRY(hipMemcpyAsync(de.col[i], job->d_out[i], bytes, hipMemcpyDeviceToHost, s));
+    if (!ea->col[i].elem) {
+      uint8_t* po = reinterpret_cast<uint8_t*>(de.off[i]);
+      st = pinned_reserve(&po, &de.off_cap[i], (n + 1) * 8);
+      de.off[i] = reinterpret_cast<uint64_t*>(po);
+      if (!st.ok()) return st;
+      HIP_TRY(hipMemcpyAsync(de.off[i], job->d_off[i], (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
+  }
+  return Status();
+}
+
 static Status emit_on_device(evql_query* q, EmitArgs& ea, const uint64_t* d_rec, uint64_t n,
                              uint32_t nwords) {
   evql_table* t = q->table;
   const KernelPlan& kp = q->rplan();
   hipStream_t s = q->ctx->stream;
   const uint32_t nsel = ea.ncols;
-  evql_query::DeviceEmit& de = q->demit;
   PackMeter pm;
   HIP_TRY(pm.begin(s));
-  de.col.resize(nsel, nullptr);
-  de.col_cap.resize(nsel, 0);
-  de.off.resize(nsel, nullptr);
-  de.off_cap.resize(nsel, 0);
-  de.elem.assign(nsel, 0);
   ea.records = d_rec;
   ea.n = n;
   ea.rw = nwords + 1;
   ea.image = t->d_image;
   bool need_first = false;
-  for (uint32_t i = 0; i < nsel; ++i) need_first = need_first || ea.col[i].kind == 2;
-  DevBuf<uint64_t> d_rows, d_vals;
-  DevBuf<uint8_t> d_tags;
-  DevBuf<RtColumn> d_cols;
-  const uint32_t nc = uint32_t(kp.cols.size());
-  if (need_first) {
-    // the column values of every group's first row (strings: their strpos words)
-    std::vector<RtColumn> rc;
-    Status stc = first_row_columns(q, &rc);
-    if (!stc.ok()) return stc;
-    HIP_TRY(d_rows.alloc(n * 8));
-    HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
-    HIP_TRY(d_vals.alloc(n * nc * 8));
-    HIP_TRY(d_tags.alloc(n * nc));
-    HIP_TRY(launch_extract_word(d_rec, n, nwords + 1, uint32_t(1 + kp.first_row_word()), d_rows, s));
-    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (rc lives until here)
-    pm.launches += 2;
-    ++pm.waits;
-    ea.first_vals = d_vals;
-    ea.first_tags = d_tags;
-  }
-  // device buffers of the packed columns
-  std::vector<DevBuf<uint8_t>> d_out(nsel);
-  std::vector<DevBuf<uint64_t>> d_off(nsel);
-  std::vector<uint64_t> str_bytes(nsel, 0);
-  DevBuf<EmitArgs> d_args;
-  HIP_TRY(d_args.alloc(sizeof(EmitArgs)));
   for (uint32_t i = 0; i < nsel; ++i) {
     EmitCol& e = ea.col[i];
-    de.elem[i] = e.elem;
-    if (e.elem) {
-      HIP_TRY(d_out[i].alloc(n * e.elem));
-      e.out = d_out[i];
-    } else {
-      e.pages = t->d_pages[kp.cols[e.src].layout_index][0];
-      HIP_TRY(d_off[i].alloc((n + 2) * 8));
-    }
+    need_first = need_first || e.kind == 2;
+    if (!e.elem) e.pages = t->d_pages[kp.cols[e.src].layout_index][0];
   }
-  HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
-  HIP_TRY(launch_emit_fixed(d_args, n, s));
-  ++pm.launches;
-  bool strings = false;
-  for (uint32_t i = 0; i < nsel; ++i) {
-    if (ea.col[i].elem) continue;
-    strings = true;
-    HIP_TRY(launch_emit_str_sizes(d_args, i, n, d_off[i], s));
-    HIP_TRY(launch_exclusive_scan(d_off[i], n, d_off[i].p + n, s));
-    HIP_TRY(hipMemcpyAsync(&str_bytes[i], d_off[i].p + n, 8, hipMemcpyDeviceToHost, s));
+  FirstRows fr;
+  if (need_first) {
+    // (no row limit: this route trusts the recorded first rows; and it waits here, where the
+    // PARTIAL route does not)
+    Status stf = gather_first_rows(q, d_rec, n, nwords + 1, kNoRowLimit, nullptr, &fr);
+    if (!stf.ok()) return stf;
+    HIP_TRY(hipStreamSynchronize(s));
     pm.launches += 2;
+    ++pm.waits;
+    ea.first_vals = fr.vals;
+    ea.first_tags = fr.tags;
   }
+  EmitColumnsJob job;
+  Status st = emit_columns_begin(q, &ea, &job);
+  if (!st.ok()) return st;
   HIP_TRY(hipStreamSynchronize(s));
   ++pm.waits;
-  if (strings) {
-    for (uint32_t i = 0; i < nsel; ++i) {
-      if (ea.col[i].elem) continue;
-      HIP_TRY(d_out[i].alloc(str_bytes[i] + 16));
-      ea.col[i].out = d_out[i];
-      ea.col[i].offsets = d_off[i];
-    }
-    HIP_TRY(hipMemcpyAsync(d_args, &ea, sizeof(EmitArgs), hipMemcpyHostToDevice, s));
-    for (uint32_t i = 0; i < nsel; ++i) {
-      if (ea.col[i].elem) continue;
-      HIP_TRY(launch_emit_str_bytes(d_args, i, n, s));
-      ++pm.launches;
-    }
-  }
-  // one copy per column into pinned host memory
-  for (uint32_t i = 0; i < nsel; ++i) {
-    const size_t bytes = ea.col[i].elem ? size_t(n) * ea.col[i].elem : size_t(str_bytes[i]);
-    Status st = pinned_reserve(&de.col[i], &de.col_cap[i], bytes);
-    if (!st.ok()) return st;
-    if (bytes) HIP_TRY(hipMemcpyAsync(de.col[i], d_out[i], bytes, hipMemcpyDeviceToHost, s));
-    if (!ea.col[i].elem) {
-      uint8_t* po = reinterpret_cast<uint8_t*>(de.off[i]);
-      st = pinned_reserve(&po, &de.off_cap[i], (n + 1) * 8);
-      de.off[i] = reinterpret_cast<uint64_t*>(po);
-      if (!st.ok()) return st;
-      HIP_TRY(hipMemcpyAsync(de.off[i], d_off[i], (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    }
-  }
+  st = emit_columns_finish(q, &ea, &job);
+  if (!st.ok()) return st;
+  pm.launches += job.launches;
   HIP_TRY(pm.mark_end(s));
   HIP_TRY(hipStreamSynchronize(s));
   ++pm.waits;
   HIP_TRY(pm.finish(&q->estats));
-  de.active = true;
+  q->demit.active = true;
   return Status();
 }
 
@@ -279,25 +296,14 @@ static Status emit_partial_on_device(evql_query* q, const PartialEmitPlan& plan,
     pa.data[i] = plan.data[i];
     if (pa.data[i].is_string) pa.data[i].pages = t->d_pages[kp.cols[pa.data[i].src].layout_index][0];
   }
-  DevBuf<uint64_t> d_rows, d_vals;
-  DevBuf<uint8_t> d_tags;
-  DevBuf<RtColumn> d_cols;
-  std::vector<RtColumn> rc;  // (lives until the first synchronisation below)
-  const uint32_t nc = uint32_t(kp.cols.size());
+  FirstRows fr;
   if (plan.need_first) {
-    // the column values of every group's first row (strings: their strpos words)
-    Status stc = first_row_columns(q, &rc);
-    if (!stc.ok()) return stc;
-    HIP_TRY(d_rows.alloc(n * 8));
-    HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
-    HIP_TRY(d_vals.alloc(n * nc * 8));
-    HIP_TRY(d_tags.alloc(n * nc));
-    HIP_TRY(launch_extract_word(d_rec, n, nwords + 1, uint32_t(1 + kp.first_row_word()), d_rows, s));
-    HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
+    // (no row limit: this route trusts the recorded first rows)
+    Status stf = gather_first_rows(q, d_rec, n, nwords + 1, kNoRowLimit, nullptr, &fr);
+    if (!stf.ok()) return stf;
     pm.launches += 2;
-    pa.first_vals = d_vals;
-    pa.first_tags = d_tags;
+    pa.first_vals = fr.vals;
+    pa.first_tags = fr.tags;
   }
   // sizes -> offsets; one wait reads both totals
   DevBuf<PartialArgs> d_args;
@@ -525,17 +531,6 @@ OrderSortInput order_sort_input(const evql_query* q, uint64_t n) {
   return in;
 }
 
-static OrderKeyArgs order_key_args(const OrderKeySpec& k) {
-  OrderKeyArgs a{};
-  a.from_ident = k.from_ident;
-  a.word = k.word;
-  a.count_word = k.count_word;
-  a.type = k.type;
-  a.is_mean = k.is_mean;
-  a.descending = k.descending;
-  return a;
-}
-
 // rows [lo, hi) of n ordered records are the result, as order_fetched has it
 static void limit_slice(const evql_query* q, uint64_t n, uint64_t* lo, uint64_t* hi) {
   *lo = 0;
@@ -577,7 +572,7 @@ static Status sort_on_device(evql_query* q, const OrderSortPlan& plan, FetchedRe
       ka.plain_word = 1;
       ka.key.word = k == 0 ? 0 : plan.base_word;
     } else {
-      ka.key = order_key_args(plan.keys[ns + 1 - k]);
+      ka.key = plan.keys[ns + 1 - k];
     }
     ka.key.records = r->d_rec;
     ka.key.record_words = rw;
@@ -678,23 +673,16 @@ static Status first_rows_from_table(evql_query* q, uint64_t n, uint32_t nwords) 
       return Status::error(EVQL_ERUNTIME, "a group's first row was not recorded");
     }
   }
-  std::vector<RtColumn> rc;
-  Status stc = first_row_columns(q, &rc);
-  if (!stc.ok()) return stc;
-  DevBuf<uint64_t> d_rows, d_vals;
-  DevBuf<RtColumn> d_cols;
-  DevBuf<uint8_t> d_tags;
-  HIP_TRY(d_rows.alloc(n * 8));
-  HIP_TRY(d_cols.alloc(nc * sizeof(RtColumn)));
-  HIP_TRY(d_vals.alloc(n * nc * 8));
-  HIP_TRY(d_tags.alloc(n * nc));
-  HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_cols, rc.data(), nc * sizeof(RtColumn), hipMemcpyHostToDevice, s));
-  HIP_TRY(launch_gather_rows(t->d_image, d_cols, nc, d_rows, n, d_vals, d_tags, s));
+  // (the rows are on the host already and checked above: they go up as they are)
+  FirstRows fr;
+  HIP_TRY(fr.rows.alloc(n * 8));
+  HIP_TRY(hipMemcpyAsync(fr.rows, rows.data(), n * 8, hipMemcpyHostToDevice, s));
+  Status stf = gather_first_rows(q, nullptr, n, 0, kNoRowLimit, nullptr, &fr);
+  if (!stf.ok()) return stf;
   q->first_vals.resize(n * nc);
   q->first_tags.resize(n * nc);
-  HIP_TRY(hipMemcpyAsync(q->first_vals.data(), d_vals, n * nc * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(q->first_tags.data(), d_tags, n * nc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(q->first_vals.data(), fr.vals, n * nc * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(q->first_tags.data(), fr.tags, n * nc, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   // bytes of the first-row strings: one packed heap per string column
   q->first_str_off.assign(n * nc, 0);
@@ -719,7 +707,7 @@ static Status first_rows_from_table(evql_query* q, uint64_t n, uint32_t nwords) 
     HIP_TRY(d_heap.alloc(bytes));
     HIP_TRY(hipMemcpyAsync(d_offs, offs.data(), n * 8, hipMemcpyHostToDevice, s));
     // (NULL rows carry strpos 0: length 0, nothing copied)
-    HIP_TRY(launch_copy_strings(t->d_image, t->d_pages[ca.layout_index][0], d_vals.p + uint64_t(c) * n,
+    HIP_TRY(launch_copy_strings(t->d_image, t->d_pages[ca.layout_index][0], fr.vals.p + uint64_t(c) * n,
                                 d_offs, n, d_heap, s));
     HIP_TRY(hipMemcpyAsync(q->first_str_heap.data() + heap0, d_heap, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1027,9 +1015,8 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
   OrderKeyArgs ok{};
   if (n > 0) {
     // (the classification is order_sort_plan.cc's: the device sort asks it of every spec)
-    OrderKeySpec k0{};
     switch (classify_order_key(q->rplan(), q->select, q->select_agg_index, q->select_passthrough,
-                               order[0], desc[0], &k0)) {
+                               order[0], desc[0], &ok)) {
       case OKEY_RECORD:
         break;
       case OKEY_EXPRESSION:
@@ -1040,7 +1027,6 @@ Status query_set_order(evql_query* q, const evql_sort_spec_t* specs, uint32_t n,
         return Status::error(EVQL_ENOTSUP,
                              "first sort expression cannot be read from a group record");
     }
-    ok = order_key_args(k0);
   }
   q->order.swap(order);
   q->order_desc.swap(desc);
@@ -1134,8 +1120,8 @@ static Status select_value(const evql_query* q, size_t i, const uint64_t* rec,
     Value av = agg_value(q, kp.aggs[q->select_agg_index[i]], rec + 1 + kp.state_word_base());
     e = eval_expr(lp.call, inputs, &av, out);
   } else if (q->select_passthrough[i]) {
-    const bool null_key = rec[0] == 2;
-    out->bits = null_key ? 0 : rec[1];
+    bool null_key;
+    out->bits = cell_bits(ResultCell(), rec, nullptr, nullptr, 0, 0, &null_key);  // (kind 0: the key)
     out->tag = null_key ? uint8_t(EVQL_STAG_NULL) : uint8_t(0);
   } else {
     e = eval_expr(lp.call, inputs, nullptr, out);
@@ -1225,28 +1211,10 @@ static void pack_direct(evql_query* q, const EmitArgs& ea, size_t max_rows, evql
     out.resize(size_t(m) * e.elem);  // (keeps its capacity from batch to batch)
     uint8_t* p = out.data();
     for (uint64_t g = 0; g < m; ++g, p += e.elem) {
-      const uint64_t* rec = rec0 + g * rw;
-      uint64_t bits;
-      uint8_t tag = 0;
-      if (e.kind == 0) {
-        const bool null_key = rec[0] == 2;
-        bits = null_key ? 0 : rec[1];
-        tag = null_key ? uint8_t(EVQL_STAG_NULL) : uint8_t(0);
-      } else {
-        bits = rec[e.word];
-        if (e.count_word >= 0) {  // min / max / mean: NULL without a non-NULL input
-          const uint64_t cnt = rec[e.count_word];
-          if (cnt == 0) {
-            bits = 0;
-            tag = EVQL_STAG_NULL;
-          } else if (e.is_mean) {
-            double sum;
-            memcpy(&sum, &bits, 8);
-            const double mean = sum / double(cnt);
-            memcpy(&bits, &mean, 8);
-          }
-        }
-      }
+      // (no first-row cell gets here: direct_pack_columns)
+      bool null;
+      const uint64_t bits = cell_bits(e, rec0 + g * rw, nullptr, nullptr, 0, 0, &null);
+      const uint8_t tag = null ? uint8_t(EVQL_STAG_NULL) : uint8_t(0);
       if (e.elem == 2) {
         p[0] = bits ? 1 : 0;
         p[1] = tag;

@@ -671,6 +671,40 @@ struct FetchedRecords {
   uint64_t total = 0;         // groups of the result before LIMIT
 };
 Status collect_records(evql_query* q, FetchedRecords* r);
+// The value of every scan column at every group's first row, as the result kernels read it
+// (result_cell.h, kind 2).  `host_cols` is the source of an asynchronous copy: a FirstRows
+// lives until the stream has been synchronised behind gather_first_rows, and as long as a
+// kernel reads vals / tags.
+struct FirstRows {
+  DevBuf<uint64_t> rows;  // [n] the first row of every group
+  DevBuf<uint64_t> vals;  // [scan column][n] value words (strings: len << 40 | position)
+  DevBuf<uint8_t> tags;   // [scan column][n] bit 0: NULL
+  DevBuf<RtColumn> cols;
+  std::vector<RtColumn> host_cols;
+};
+static const uint64_t kNoRowLimit = ~0ull;
+// Two kernels, no wait.  The rows are word 1 + first_row_word of the n records at d_rec, rw
+// words each -- with a row_limit, a row at or behind it reads as NULL and raises status[1]
+// (k_mat_first_rows) -- or, where d_rec is NULL, what the caller has put into fr->rows.
+Status gather_first_rows(evql_query* q, const uint64_t* d_rec, uint64_t n, uint32_t rw,
+                         uint64_t row_limit, uint64_t* d_status, FirstRows* fr);
+// the pinned buffer *p of *cap bytes holds at least `bytes` (grown with some slack)
+Status pinned_reserve(uint8_t** p, size_t* cap, size_t bytes);
+// One packing of an EmitArgs column set (n, ncols, the cells, elem and -- for strings -- pages
+// filled in) as SVector bytes into q->demit, in two phases; the caller owns the wait in
+// between, which brings the string totals to the host, and the one behind the second.  The job
+// lives until that one.
+struct EmitColumnsJob {
+  std::vector<DevBuf<uint8_t>> d_out;
+  std::vector<DevBuf<uint64_t>> d_off;
+  std::vector<uint64_t> str_bytes;
+  DevBuf<EmitArgs> d_args;
+  uint32_t launches = 0;  // kernels enqueued so far
+};
+// buffers, the fixed-width kernel, then sizes, scan and total per string column
+Status emit_columns_begin(evql_query* q, EmitArgs* ea, EmitColumnsJob* job);
+// heaps and bytes kernels of the string columns, one pinned copy per column
+Status emit_columns_finish(evql_query* q, EmitArgs* ea, EmitColumnsJob* job);
 // materialize.cc: evql_table_from_query
 MatInput materialize_input(const evql_query* q, const std::vector<MatSpec>* specs, int sort_column);
 Status table_from_query(evql_query* q, const std::vector<ColumnSpec>& specs, int sort_column,

@@ -170,7 +170,8 @@ def test_host_only_plan_under_sanitizers(tmp_path):
     subprocess.check_call([cxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", "-I", CSRC,
                            os.path.join(ROOT, "tools", "materialize_plan_check.cc"),
-                           os.path.join(CSRC, "materialize_plan.cc"), "-o", exe])
+                           os.path.join(CSRC, "materialize_plan.cc"),
+                           os.path.join(CSRC, "result_cell.cc"), "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert p.returncode == 0 and p.stdout.strip() == "ok", p.stderr[-2000:]
 

@@ -207,7 +207,7 @@ int main() {
     Fixture f(EVQL_T_UINT64, fns, types, false, 2);
     f.by({{1, false}, {3, false}});
     EXPECT(f.decide(&p) == OSORT_UNREADABLE);
-    OrderKeySpec k{};
+    OrderKeyArgs k{};
     EXPECT(classify_order_key(f.kp, f.select, f.agg_index, f.passthrough, f.order[1], false, &k) ==
            OKEY_EXACT_SUM);
     EXPECT(classify_order_key(f.kp, f.select, f.agg_index, f.passthrough, f.order[0], true, &k) ==
