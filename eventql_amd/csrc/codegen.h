@@ -109,6 +109,14 @@ struct KernelPlan {
   // prefetching kernel of the plan has compiled with scratch memory (compile_plan_kernels).
   bool prefetch = false;
   bool prefetch_allowed = false;
+  // The staging form of the prefetching loop (codegen_kernels.inc stage_step):
+  // every row runs WHERE only and the passing rows leave what the group key and the aggregate
+  // arguments read (stage_tuple_layout) in a ring of the wave in LDS; the group table is
+  // updated once per 64 staged rows, with a full exec mask.  Chosen by choose_launch_shape
+  // among the prefetching plans where `stage_allowed`: false under EVQL_SCAN_STAGE=0
+  // (build_kernel_plan) and once the staging kernel has compiled with scratch memory.
+  bool stage = false;
+  bool stage_allowed = false;
   // high cardinality: radix-partition the passing rows into 2^part_bits buckets
   // of tuples, then aggregate each bucket in LDS (codegen_kernels.inc)
   bool partitioned = false;
@@ -142,6 +150,25 @@ struct KernelPlan {
   std::vector<ZoneConjunct> zone_conjuncts;
   int tile_rows() const { return block * 2 * unroll; }
 };
+
+// One field of a staged tuple: scan column `col` as the bits of its copy (8-bit values take a
+// 16-bit field), at bit `shift` of 32-bit word `word`.
+struct StageField {
+  int col = -1;
+  int bits = 0;
+  bool f32 = false;  // the raw word of a float32 copy, widened again behind the ring
+  int word = 0;
+  int shift = 0;
+};
+// Entries of a wave's staging ring: at most 63 tuples are pending when a row is staged, and
+// a row adds at most 64.
+static const int kStageRing = 128;
+// LDS bytes a workgroup may have (gfx950)
+static const uint64_t kLdsBytes = 160 * 1024;
+// The tuple of a staging plan: the columns the group key and the aggregate arguments read, by
+// column index, two fields of <= 16 bits to a word first, the 32-bit fields behind them.
+// Returns its 32-bit words.
+int stage_tuple_layout(const KernelPlan& kp, std::vector<StageField>* fields);
 
 // launch shape for `hint` expected groups (planner.cc)
 void choose_launch_shape(KernelPlan* kp, uint64_t hint);

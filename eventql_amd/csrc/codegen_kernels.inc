@@ -195,8 +195,33 @@ struct Gen {
   size_t n_literals = 0;  // of evql_eval_row
   // numeric literals are numbered once per plan, across its row functions (A.lit[i])
   std::vector<uint64_t> pool;
+  // (a staging plan: the staging loop of its scan kernel, prefetch_tile_loop)
+  bool staged() const { return kp.stage && kp.prefetch; }
   void eval_row() {
-    n_literals = row_function(0, [&](Emitter& em) { eval_row_body(em); });
+    if (!staged()) {
+      n_literals = row_function(0, [&](Emitter& em) { eval_row_body(em); });
+      return;
+    }
+    // A staging plan evaluates a row in two places: WHERE for every row (evql_where_row), the
+    // group identity and the update operands for the rows taken out of the ring
+    // (evql_eval_post).  evql_eval_row, for the loop with zone test, is the two in a row.
+    n_literals = row_function(0, [&](Emitter& em) {
+      row_signature("bool", "evql_where_row", "valid", false);
+      where_part(em);
+      s << "  return live;\n}\n\n";
+    });
+    n_literals += row_function(n_literals, [&](Emitter& em) {
+      row_signature("void", "evql_eval_post", "live", true);
+      col_decls();
+      post_part(em);
+      s << "}\n\n";
+    });
+    row_signature("void", "evql_eval_row", "valid", true);
+    for (int pass = 0; pass < 2; ++pass) {
+      s << (pass ? "), " : "  evql_eval_post(A, row, evql_where_row(A, row, valid, ");
+      for (int i = 0; i < NC; ++i) s << (i ? ", " : "") << "r" << i << ", g" << i;
+    }
+    s << ", o);\n}\n\n";
   }
 
   // c<i>: scan column i of the row as the VM types it, from its loaded word r<i>
@@ -218,11 +243,15 @@ struct Gen {
     }
   }
 
-  void eval_row_body(Emitter& em) {
-    s << "__device__ __forceinline__ void evql_eval_row(const EvqlArgs& A, const u64 row, "
-         "const bool valid";
+  // `flag`: the name of the bool behind `row` (is the row in the window / did it pass WHERE)
+  void row_signature(const char* ret, const char* name, const char* flag, bool out) {
+    s << "__device__ __forceinline__ " << ret << " " << name << "(const EvqlArgs& A, const u64 row, "
+         "const bool " << flag;
     for (int i = 0; i < NC; ++i) s << ", const u64 r" << i << ", const u32 g" << i;
-    s << ", EvqlRowOut& o) {\n";
+    s << (out ? ", EvqlRowOut& o) {\n" : ") {\n");
+  }
+  // `live`: is the row in the window, in the row filter and does it pass WHERE
+  void where_part(Emitter& em) {
     s << "  bool live = valid;\n";
     if (kp.has_row_filter) {
       s << "  live = live && evql_row_filter(A.row_filter, A.row_filter_len, row);\n";
@@ -236,6 +265,16 @@ struct Gen {
       em.o.str("");
       s << "    live = " << p.v << ";\n  }\n";
     }
+  }
+  void eval_row_body(Emitter& em) {
+    row_signature("void", "evql_eval_row", "valid", true);
+    where_part(em);
+    post_part(em);
+    s << "}\n\n";
+  }
+  // the group identity and the update operands of a row that is `live`
+  void post_part(Emitter& em) {
+    em.ind = "    ";
     s << "  o.live = live;\n  o.knull = false;\n  o.ident = 0;\n  o.ident2 = 0;\n";
     for (int i = 0; i < U(); ++i) {
       s << "  o.ub[" << i << "] = evql_op_identity<" << op_name(updw[i].op) << ">(); o.uc[" << i
@@ -325,7 +364,7 @@ struct Gen {
         }
       }
     }
-    s << "  }\n}\n\n";
+    s << "  }\n";
   }
 
   // loads of one tile into x<i>[u][j] / y<i>[u][j]; `only`: of these columns alone
@@ -538,6 +577,98 @@ struct Gen {
     s << "\n" << ind << "}\n";
   }
 
+  // ---- the staging form of the prefetching loop (KernelPlan::stage) ------------------------
+  // The evaluation of a tile in two halves.  STAGE, for every row: WHERE on the row's values
+  // (evql_where_row); the lanes whose row passes put a tuple into the wave's ring in LDS
+  // (evql_device.h evql_stage_put).  DRAIN, whenever 64 tuples are pending: every lane takes
+  // one, evaluates the group identity and the update operands from it (evql_eval_post) and
+  // updates the group table with evql_update, as the other loops do -- with all 64 lanes at
+  // work, where the row's own exec mask has as many as WHERE lets pass.
+  //
+  // The tuple holds the columns that the group key and the aggregate arguments read, each as
+  // the bits of its copy (stage_tuple_layout): what a row function computes from them it
+  // computes behind the ring, so a tuple is never wider than the row's loaded words, a float32
+  // copy travels as its raw word (widened by evql_f32_dec as in the other loops, bit for bit)
+  // and tags, NULL keys and skipped updates need no bits of their own.
+  std::vector<StageField> sfields;
+  int stage_words = 0;
+  // field `f` of row j of the step, from the raw words of tile C
+  static std::string stage_raw_field(const StageField& f, int j) {
+    const std::string c = "c" + std::to_string(f.col) + "[u]";
+    if (f.bits == 32) return c + "[" + std::to_string(j) + "]";
+    const std::string m = f.bits == 16 ? "0xffffu" : "0xffu";
+    return "((" + c + "[0] >> " + std::to_string(f.bits * j) + ") & " + m + ")";
+  }
+  // EvqlStaged, its pack (one argument per field, in the layout's order) and, per staged
+  // column, the value the row function takes
+  void stage_tuple_text() {
+    stage_words = stage_tuple_layout(kp, &sfields);
+    s << "struct alignas(" << (stage_words % 2 == 0 ? 8 : 4) << ") EvqlStaged { u32 w[" << stage_words
+      << "]; };\n";
+    s << "__device__ __forceinline__ EvqlStaged evql_stage_pack(";
+    for (size_t k = 0; k < sfields.size(); ++k) s << (k ? ", " : "") << "const u32 f" << k;
+    s << ") {\n  EvqlStaged t;\n";
+    for (int w = 0; w < stage_words; ++w) {
+      s << "  t.w[" << w << "] = ";
+      bool first = true;
+      for (size_t k = 0; k < sfields.size(); ++k) {
+        if (sfields[k].word != w) continue;
+        s << (first ? "" : " | ");
+        if (sfields[k].shift) s << "(f" << k << " << " << sfields[k].shift << ")";
+        else s << "f" << k;
+        first = false;
+      }
+      s << ";\n";
+    }
+    s << "  return t;\n}\n";
+    for (const StageField& f : sfields) {
+      s << "__device__ __forceinline__ u64 evql_stage_col" << f.col << "(const EvqlStaged& t) {\n";
+      if (f.f32) {
+        s << "  u64 v0, v1;\n  evql_f32_dec(t.w[" << f.word << "], t.w[" << f.word << "], v0, v1);\n  return v0;\n";
+      } else if (f.bits == 32) {
+        s << "  return (u64) evql_opaque(t.w[" << f.word << "]);\n";
+      } else {
+        s << "  return (u64) evql_opaque((t.w[" << f.word << "] >> " << f.shift << ") & 0xffffu);\n";
+      }
+      s << "}\n";
+    }
+    s << "\n";
+  }
+  // 64 tuples, or the `live` lanes' at the end of the kernel, out of the ring and into the table
+  void stage_drain_function() {
+    s << "__device__ __forceinline__ void evql_stage_drain(const EvqlArgs& A, u64* lds, const EvqlStaged* ring,\n"
+         "                                                 EvqlAcc& acc, const bool bypass, u32& head, "
+         "const u32 lane, const bool live) {\n";
+    s << "  const EvqlStaged t = evql_stage_take(ring, head, lane);\n";
+    s << "  EvqlRowOut o;\n  evql_eval_post(A, 0ull, live";
+    for (int i = 0; i < NC; ++i) {
+      bool in = false;
+      for (const StageField& f : sfields) in = in || f.col == i;
+      if (in) s << ", evql_stage_col" << i << "(t), 0u";
+      else s << ", 0ull, 0u";
+    }
+    s << ", o);\n";
+    s << "  const u64 k = evql_lds_peek(&lds[(u32) o.ident & (EVQL_LDS_SLOTS - 1)]);\n";
+    s << "  evql_update(A, lds, acc, bypass, 0ull, o, k);\n}\n\n";
+  }
+  // rows (u, 0) and (u, 1) of the tile held raw in C.  Drain first, then stage: at most 63
+  // tuples are pending when a row puts its own, at most 64, into EVQL_STAGE_RING = 128 entries
+  // (and the copy's wait for the next tile then follows a row's few staging instructions, not
+  // the cold block of a drain's HBM updates).
+  void stage_step(const std::string& ind) {
+    const char* in = ind.c_str();
+    for (int j = 0; j < 2; ++j) {
+      s << in << "if (tail - head >= 64u) evql_stage_drain(A, lds, ring, acc, bypass, head, lane, true);\n";
+      s << in << "const bool l" << j << " = evql_where_row(A, r + " << j << ", wrel + (u32) (u * EVQL_BLOCK * 2 + "
+        << j << ") < wlen";
+      for (int i = 0; i < NC; ++i) s << ", x" << i << "s[" << j << "], 0u";
+      s << ");\n";
+      s << in << "evql_stage_put(ring, tail, l" << j << ", evql_stage_pack(";
+      for (size_t k = 0; k < sfields.size(); ++k) s << (k ? ", " : "") << stage_raw_field(sfields[k], j);
+      s << "));\n";
+    }
+  }
+
   // ---- the fused scan kernel --------------------------------------------------------
   // (the tile loop reads the identity slots of a step's two rows ahead of their updates)
   bool probe_ahead() const { return grouped && S > 0 && !kp.has_ident2(); }
@@ -578,6 +709,11 @@ struct Gen {
     s << "  u32 tile_no = 0;  // tiles evaluated\n";
     raw_tile_decls("  ", "c", false);
     s << "  bool have = false;\n  u64 tc = 0;\n";
+    if (staged()) {
+      s << "  EvqlStaged* const ring = evql_stage_ring + (tid >> 6) * EVQL_STAGE_RING;\n";
+      s << "  const u32 lane = tid & 63u;\n";
+      s << "  u32 head = 0, tail = 0;  // tuples this wave has taken out of its ring / put into it\n";
+    }
     s << "  for (u64 t = blockIdx.x; have || t < A.ntiles; t += gridDim.x) {\n";
     s << "    const bool more = t < A.ntiles;\n";
     s << "    const u64 tl = more ? t : tc;\n";
@@ -596,7 +732,8 @@ struct Gen {
     s << "#pragma unroll\n      for (int u = 0; u < EVQL_UNROLL; ++u) {\n";
     s << "        const u64 r = base + ((u64) (u * EVQL_BLOCK) + tid) * 2;\n";
     raw_step_decode("        ");
-    scan_step("        ", true);
+    if (staged()) stage_step("        ");
+    else scan_step("        ", true);
     s << "      }\n      ++tile_no;\n    }\n";
     s << "    __builtin_amdgcn_sched_barrier(0);\n";
     raw_tile_copy("    ");
@@ -610,6 +747,17 @@ struct Gen {
     s << "    tc = tl;\n    have = more;\n";
     s << "    if (__builtin_amdgcn_readfirstlane(st) & EVQL_ST_TABLE_FULL) break;\n";
     s << "  }\n";
+    if (staged()) {
+      // what is still pending behind the last tile: up to 63 + 64 tuples.  (Behind a
+      // TABLE_FULL break too: that launch is void either way.)
+      s << "  {\n";
+      s << "    const bool bypass = evql_lds_peek32(reinterpret_cast<const u32*>(&lds[EVQL_WORDS * "
+           "EVQL_LSTRIDE])) >= 4u * EVQL_BLOCK;\n";
+      s << "    if (tail - head >= 64u) evql_stage_drain(A, lds, ring, acc, bypass, head, lane, true);\n";
+      s << "    const u32 left = tail - head;\n";
+      s << "    if (left) evql_stage_drain(A, lds, ring, acc, bypass, head, lane, lane < left);\n";
+      s << "  }\n";
+    }
   }
   void scan_kernel() {
     // (passed / spilled: rows of this lane.  A plan with the prefetching loop counts them in 32
@@ -844,10 +992,17 @@ struct Gen {
       s << "  }\n}\n\n";
     }
 
+    if (staged()) {
+      stage_tuple_text();
+      stage_drain_function();
+    }
+
     s << "extern \"C\" __global__ void __launch_bounds__(EVQL_BLOCK) evql_scan_agg(const EvqlArgs A) {\n";
     s << "  const u32 tid = threadIdx.x;\n";
     if (grouped && S > 0) {
       s << "  __shared__ u64 lds[EVQL_WORDS * EVQL_LSTRIDE + 1];\n";
+      // (a ring of tuples per wave, behind the table: the staging loop)
+      if (staged()) s << "  __shared__ EvqlStaged evql_stage_ring[(EVQL_BLOCK / 64) * EVQL_STAGE_RING];\n";
       s << "  evql_lds_init(lds);\n  __syncthreads();\n";
     } else {
       s << "  u64* lds = nullptr;\n";

@@ -523,6 +523,31 @@ __device__ __forceinline__ u32 evql_lds_peek32(const u32* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// The staging ring of a wave (the staging tile loop of evql_scan_agg): the
+// rows that pass WHERE leave a tuple each in EVQL_STAGE_RING entries of LDS that only this
+// wave touches, and the wave takes them out again 64 at a time, one to a lane.  `head` and
+// `tail` count the tuples taken and put since the kernel began, modulo 2^32; they derive from
+// ballots alone and so stay on the scalar unit.  The caller takes 64 out whenever 64 are
+// pending BEFORE it puts a row's, so at most 63 + 64 are ever held.  One wave's LDS
+// operations complete in the order they were issued: the fence and the wave barrier only keep
+// the compiler from moving the reads ahead of the writes.
+#define EVQL_STAGE_RING 128u
+template <typename T>
+__device__ __forceinline__ void evql_stage_put(T* ring, u32& tail, const bool live, const T& t) {
+  const u64 m = __builtin_amdgcn_ballot_w64(live);
+  const u32 below = __builtin_amdgcn_mbcnt_hi((u32) (m >> 32), __builtin_amdgcn_mbcnt_lo((u32) m, 0u));
+  if (live) ring[(tail + below) & (EVQL_STAGE_RING - 1u)] = t;
+  tail += (u32) __builtin_popcountll(m);
+}
+template <typename T>
+__device__ __forceinline__ T evql_stage_take(const T* ring, u32& head, const u32 lane) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const T t = ring[(head + lane) & (EVQL_STAGE_RING - 1u)];
+  head += 64u;
+  return t;
+}
+
 // LDS table: returns the slot or -1 when no slot was found within MAXP probes
 // `cur`: the word of the identity slot keys[ident & mask] as the caller read it (evql_lds_peek),
 // possibly a while ago: a key never changes once written, and an EVQL_EMPTY that has been

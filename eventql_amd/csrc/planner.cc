@@ -308,12 +308,47 @@ bool partitioned_path_possible(const KernelPlan& kp) {
 // the partitioned path takes over as soon as the expected groups exceed the LDS slots
 const uint64_t kPartitionAboveSlots = 1;
 
+int stage_tuple_layout(const KernelPlan& kp, std::vector<StageField>* fields) {
+  std::vector<uint32_t> used;
+  for (const auto& g : kp.group) expr_inputs(g, &used);
+  for (const auto& a : kp.aggs) {
+    if (a.arg) expr_inputs(a.arg, &used);
+  }
+  std::vector<bool> staged(kp.cols.size(), false);
+  for (uint32_t u : used) {
+    if (u < kp.cols.size()) staged[u] = true;
+  }
+  if (fields) fields->clear();
+  int halves = 0, words = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (size_t i = 0; i < kp.cols.size(); ++i) {
+      const ColAccess& c = kp.cols[i];
+      if (!staged[i] || (c.bits == 32) != (pass == 1)) continue;
+      StageField f;
+      f.col = int(i);
+      f.bits = int(c.bits);
+      f.f32 = c.mode == ColAccess::NARROW_F32;
+      if (pass == 0) {
+        f.word = halves / 2;
+        f.shift = 16 * (halves % 2);
+        ++halves;
+        words = (halves + 1) / 2;
+      } else {
+        f.word = words++;
+      }
+      if (fields) fields->push_back(f);
+    }
+  }
+  return words;
+}
+
 void choose_launch_shape(KernelPlan* kpp, uint64_t hint) {
   KernelPlan& kp = *kpp;
   kp.block = 256;
   kp.partitioned = false;
   kp.lane_cache = 1;
   kp.prefetch = false;
+  kp.stage = false;
   // loads in flight per lane = columns x unroll; ~16 saturate HBM (measured: 2
   // columns 2.54 ms at unroll 4, 2.43 ms at unroll 8; 4 columns spill at 8)
   kp.unroll = kp.cols.size() <= 2 ? 8 : 4;
@@ -391,6 +426,20 @@ void choose_launch_shape(KernelPlan* kpp, uint64_t hint) {
             !c.has_tags && (c.bits == 8 || c.bits == 16 || c.bits == 32);
     }
     kp.prefetch = raw;
+    // The staging form of that loop: WHERE alone runs for every row, the update of the group
+    // table once per 64 rows that passed.  It pays where WHERE rejects rows -- with 64 rows to
+    // a wave instruction some lane nearly always passes, so the update path otherwise runs for
+    // every row at the exec mask of the few that pass -- and only costs where there is no
+    // WHERE.  The tuple carries no row number (no first-row column), and a wave's ring of
+    // tuples has to fit the LDS beside the table: 12-byte tuples do beside 4096 slots of 4
+    // words, 16-byte tuples do not.
+    if (raw && kp.stage_allowed && kp.where && !expr_always_true(kp.where) && !kp.need_first_row &&
+        !kp.has_ident2()) {
+      const uint64_t table = (uint64_t(kp.words_per_slot()) * (s + 2) + 1) * 8;
+      const uint64_t words = uint64_t(stage_tuple_layout(kp, nullptr));
+      const uint64_t ring = uint64_t(kp.block / 64) * kStageRing * 4 * words;
+      kp.stage = words >= 1 && table + ring <= kLdsBytes;
+    }
     // (measured, round 2: a 2048-slot table runs dense keys as fast as 4096 slots, but the
     //  freed LDS does not buy a second workgroup per CU: at 64 VGPRs per wave the kernel
     //  spills -- config 3 over 16-bit pages 0.38 -> 1.03 ms; with unroll 2 on top 0.50 ms,
@@ -910,6 +959,9 @@ Status build_kernel_plan(const TableLayout& layout, const evql_plan_desc_t* plan
   // the loop that waits for a tile's loads before it evaluates the tile.
   const char* pf = getenv("EVQL_SCAN_PREFETCH");
   kp.prefetch_allowed = !nested && !(pf && strcmp(pf, "0") == 0);
+  // ... and its staging form; EVQL_SCAN_STAGE=0 keeps the prefetching loop as it was.
+  const char* sg = getenv("EVQL_SCAN_STAGE");
+  kp.stage_allowed = kp.prefetch_allowed && !(sg && strcmp(sg, "0") == 0);
 
   choose_launch_shape(&kp, plan->groups_hint);
   return Status();

@@ -129,6 +129,19 @@ static Status compile_plan_kernels(evql_query* q) {
   q->source = generate_kernel_source(&q->kp);
   Status st = compile_kernel(ctx, q->source, &q->module, true);
   if (!st.ok()) return st;
+  if (q->kp.stage) {
+    // The staging loop adds a tuple and its ring address to what the prefetching loop holds.
+    // Where that does not fit the registers, the plan keeps the prefetching loop.
+    int sc = 0;
+    if (q->module.fn &&
+        hipFuncGetAttribute(&sc, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, q->module.fn) == hipSuccess && sc != 0) {
+      q->kp.stage = false;
+      q->kp.stage_allowed = false;
+      q->source = generate_kernel_source(&q->kp);
+      st = compile_kernel(ctx, q->source, &q->module, true);
+      if (!st.ok()) return st;
+    }
+  }
   if (q->kp.prefetch) {
     // The prefetching tile loop holds two raw tiles.  Where that does not fit the registers,
     // the plan keeps the plain loop at its unroll (and keeps it when it is re-shaped) rather
